@@ -16,7 +16,10 @@ test-gpu:
 bench:
 	python bench.py --gpus 1 --steps 50 --warmup 10
 
+bench-full:
+	python bench.py --gpus 1 --steps 50 --warmup 10 --full
+
 clean:
 	$(MAKE) -C native clean
 
-.PHONY: all native tsan test test-gpu bench clean
+.PHONY: all native tsan test test-gpu bench bench-full clean

@@ -104,29 +104,28 @@ class TestValidatorCatchesRealMistakes:
         assert errs and "no pinned schema" in str(errs[0])
 
 
-class TestReferenceManifestsAgainstModernSchema:
-    """The validator applied to the REFERENCE's own manifests: its HPA uses
-    autoscaling/v2beta1 (reference cuda-test-hpa.yaml:1), which modern
-    clusters (>=1.26) reject — exactly the apply-time failure this stack's
-    rewritten manifest avoids. The validator must reproduce that verdict."""
-
-    REF = Path("/root/reference")
-
-    def test_reference_hpa_rejected_for_v2beta1(self):
-        if not (self.REF / "cuda-test-hpa.yaml").exists():
-            pytest.skip("reference tree not present")
-        doc = yaml.safe_load((self.REF / "cuda-test-hpa.yaml").read_text())
-        errors = validate_manifest(doc)
-        assert any("autoscaling/v2beta1" in str(e) for e in errors), errors
-
-    def test_reference_deployment_validates(self):
-        # the workload manifest itself is schema-clean (only the GPU
-        # resource name differs from ours)
-        if not (self.REF / "cuda-test-deployment.yaml").exists():
-            pytest.skip("reference tree not present")
-        doc = yaml.safe_load(
-            (self.REF / "cuda-test-deployment.yaml").read_text())
-        assert validate_manifest(doc) == []
+def test_foreign_gpu_deployment_validates():
+    """The validator accepts a valid Deployment that is not one of ours: a
+    workload asking for another vendor's GPU resource name is schema-clean."""
+    labels = {"app": "vector-job"}
+    doc = {
+        "apiVersion": "apps/v1",
+        "kind": "Deployment",
+        "metadata": {"name": "vector-job", "labels": dict(labels)},
+        "spec": {
+            "selector": {"matchLabels": dict(labels)},
+            "template": {
+                "metadata": {"labels": dict(labels)},
+                "spec": {"containers": [{
+                    "name": "worker",
+                    "image": "registry.example.com/vector-job:1.0",
+                    "command": ["/bin/worker", "--iterations", "100"],
+                    "resources": {"limits": {"nvidia.com/gpu": 1}},
+                }]},
+            },
+        },
+    }
+    assert validate_manifest(doc) == []
 
 
 def test_cli_validates_shipped_manifests(tmp_path):

@@ -14,6 +14,7 @@ import json
 import os
 import struct
 from concurrent import futures
+from pathlib import Path
 
 import pytest
 
@@ -24,6 +25,15 @@ SAMPLER_LIB = str(NATIVE_BUILD / "libmi355x_sampler.so")
 needs_lib = pytest.mark.skipif(
     not os.path.exists(SAMPLER_LIB), reason="libmi355x_sampler.so not built"
 )
+
+
+@pytest.fixture()
+def sock_dir(tmp_path, monkeypatch):
+    """Directory for unix sockets. sockaddr_un.sun_path holds 107 bytes and
+    pytest's tmp_path can be longer than that, so run from tmp_path and
+    name the sockets relative to it (child processes inherit the cwd)."""
+    monkeypatch.chdir(tmp_path)
+    return Path(".")
 
 
 def _lib():
@@ -126,7 +136,7 @@ class TestProtobufWalker:
 @needs_lib
 class TestAgainstRealGrpcServer:
     @pytest.fixture()
-    def grpc_socket(self, tmp_path):
+    def grpc_socket(self, sock_dir):
         grpc = pytest.importorskip("grpc")
 
         class Handler(grpc.GenericRpcHandler):
@@ -139,7 +149,7 @@ class TestAgainstRealGrpcServer:
                     )
                 return None
 
-        sock = tmp_path / "kubelet.sock"
+        sock = sock_dir / "kubelet.sock"
         server = grpc.server(futures.ThreadPoolExecutor(max_workers=2))
         server.add_generic_rpc_handlers((Handler(),))
         server.add_insecure_port(f"unix:{sock}")
@@ -158,11 +168,11 @@ class TestAgainstRealGrpcServer:
         gpu_allocs = [a for a in allocs if a["resource"] == "amd.com/gpu"]
         assert {a["pod"] for a in gpu_allocs} == {"cuda-test-abc", "cuda-test-def"}
 
-    def test_missing_socket_fails_cleanly(self, tmp_path):
+    def test_missing_socket_fails_cleanly(self, sock_dir):
         lib = _lib()
         buf = ctypes.create_string_buffer(4096)
         rc = lib.mi355x_list_pod_resources_json(
-            str(tmp_path / "nope.sock").encode(), buf, len(buf)
+            str(sock_dir / "nope.sock").encode(), buf, len(buf)
         )
         assert rc == -1
         assert b"connect" in buf.value
@@ -173,7 +183,7 @@ class TestExporterK8sMode:
     """Full integration: exporter -k against the fake kubelet; pod labels
     appear on the metrics (the DCGM_EXPORTER_KUBERNETES analog)."""
 
-    def test_pod_labels_on_metrics(self, tmp_path):
+    def test_pod_labels_on_metrics(self, sock_dir):
         grpc = pytest.importorskip("grpc")
         import time as _time
 
@@ -200,7 +210,7 @@ class TestExporterK8sMode:
 
         state = {"response": response}
 
-        sock = tmp_path / "kubelet.sock"
+        sock = sock_dir / "kubelet.sock"
         server = grpc.server(futures.ThreadPoolExecutor(max_workers=2))
 
         class MutableHandler(grpc.GenericRpcHandler):

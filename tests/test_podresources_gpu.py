@@ -58,9 +58,14 @@ def _real_device_identity():
 
 
 @pytest.mark.parametrize("id_type", ["device-name", "uuid"])
-def test_attribution_with_real_device_ids(gpu, tmp_path, id_type):
+def test_attribution_with_real_device_ids(gpu, tmp_path, monkeypatch, id_type):
     from mi355x_gpu_hpa.control import parse_prometheus_text
     from mi355x_gpu_hpa.exporter import ExporterProcess
+
+    # sockaddr_un.sun_path holds 107 bytes and tmp_path can be longer: run
+    # from tmp_path and name the socket relative to it (the exporter child
+    # inherits the cwd)
+    monkeypatch.chdir(tmp_path)
 
     render, uuid = _real_device_identity()
     assert render.startswith("renderD"), render
@@ -72,7 +77,7 @@ def test_attribution_with_real_device_ids(gpu, tmp_path, id_type):
             container("main", [container_devices("amd.com/gpu", [device_id])]),
         ]),
     ])
-    sock = tmp_path / "kubelet.sock"
+    sock = "kubelet.sock"
     server = _serve(str(sock), response)
     try:
         with ExporterProcess(
