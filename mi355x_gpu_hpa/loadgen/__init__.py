@@ -1,7 +1,9 @@
 """ctypes bindings for the CDNA4 HIP load-generator library.
 
-Native side: native/loadgen/{vector_add,gemm_bf16}.hip + loadgen_lib.cpp,
-built by ``make -C native loadgen`` into native/build/libmi355x_loadgen.so.
+Native side: native/loadgen/{vector_add,gemm_bf16,gemm_fp8_256,
+gemm_mxfp4_256}.hip + loadgen_lib.cpp, built by ``make -C native loadgen``
+into native/build/libmi355x_loadgen.so. The MXFP4 quantizer is also built
+on its own, without HIP, into native/build/libmi355x_mxfp4.so.
 
 These are the MI355X-native replacements for the reference's CUDA workload
 (`k8s.gcr.io/cuda-vector-add:v0.1`, cuda-test-deployment.yaml:18-19).
@@ -22,6 +24,9 @@ from .. import NATIVE_BUILD
 
 _LIB_PATH = os.environ.get(
     "MI355X_LOADGEN_LIB", str(NATIVE_BUILD / "libmi355x_loadgen.so")
+)
+_MXFP4_LIB_PATH = os.environ.get(
+    "MI355X_MXFP4_LIB", str(NATIVE_BUILD / "libmi355x_mxfp4.so")
 )
 
 
@@ -102,12 +107,42 @@ def _load():
             np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
             ctypes.c_int, ctypes.c_int, ctypes.c_int,
         ]
+        lib.lg_gemm_mxfp4_burn.argtypes = lib.lg_gemm_burn.argtypes
+        lib.lg_gemm_mxfp4_bench.argtypes = lib.lg_gemm_bf16_bench.argtypes
+        lib.lg_gemm_mxfp4_verify.argtypes = (
+            lib.lg_gemm_fp8_verify.argtypes + [ctypes.c_int]
+        )
         lib.lg_bw_burn.argtypes = [
             ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
             ctypes.c_double, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
         ]
         _lib = lib
     return _lib
+
+
+_mxfp4_lib = None
+
+
+def _load_mxfp4():
+    """The host-only MXFP4 quantizer library (no HIP dependency)."""
+    global _mxfp4_lib
+    if _mxfp4_lib is None:
+        if not os.path.exists(_MXFP4_LIB_PATH):
+            raise LoadgenError(
+                f"libmi355x_mxfp4.so not found at {_MXFP4_LIB_PATH}; "
+                "run `make -C native mxfp4-host`"
+            )
+        lib = ctypes.CDLL(_MXFP4_LIB_PATH)
+        lib.lg_mxfp4_last_error.restype = ctypes.c_char_p
+        lib.lg_mxfp4_quantize.argtypes = [
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            ctypes.c_int, ctypes.c_int,
+            np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.uint8, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+        ]
+        _mxfp4_lib = lib
+    return _mxfp4_lib
 
 
 def _check(rc: int):
@@ -197,12 +232,68 @@ def gemm_fp8_bench(m=8192, n=8192, k=8192, warmup=2, iters=10, raster=1,
     return ms.value, tf.value
 
 
+def mxfp4_quantize(x: np.ndarray):
+    """OCP MX FP4 quantizer (host only, no GPU needed): x f32 [r, k] with
+    k % 32 == 0 -> (packed u8 [r, k/2], scales u8 [r, k/32], deq f32 [r, k]).
+
+    packed[r, i] holds element 2i in bits 3:0 and 2i+1 in bits 7:4 (E2M1
+    codes); scales[r, b] is the E8M0 byte (value 2^(byte-127)) of elements
+    32b..32b+31; deq is what those bytes decode to. Non-finite input
+    raises LoadgenError."""
+    x = np.ascontiguousarray(x, np.float32)
+    if x.ndim != 2:
+        raise LoadgenError("mxfp4_quantize expects a 2-D array")
+    r, k = x.shape
+    packed = np.empty((r, k // 2), np.uint8)
+    scales = np.empty((r, k // 32), np.uint8)
+    deq = np.empty((r, k), np.float32)
+    lib = _load_mxfp4()
+    if lib.lg_mxfp4_quantize(x, r, k, packed, scales, deq) != 0:
+        raise LoadgenError(lib.lg_mxfp4_last_error().decode())
+    return packed, scales, deq
+
+
+def gemm_mxfp4(a: np.ndarray, bt: np.ndarray, device: int = 0,
+               max_ctas: int = 0):
+    """MXFP4 (E2M1 + E8M0 block scale) MFMA GEMM numerics entry: quantizes
+    the f32 inputs like mxfp4_quantize(), computes C = Aq @ Btq^T on the
+    GPU, and returns (c, aq, btq) where aq/btq are the dequantized (f32)
+    operands the GPU actually multiplied. M,N,K % 256 == 0. max_ctas > 0
+    caps the grid so each CTA loops over several tiles."""
+    m, k = a.shape
+    n, k2 = bt.shape
+    assert k == k2
+    a = np.ascontiguousarray(a, np.float32)
+    bt = np.ascontiguousarray(bt, np.float32)
+    c = np.empty((m, n), np.float32)
+    aq = np.empty_like(a)
+    btq = np.empty_like(bt)
+    _check(_load().lg_gemm_mxfp4_verify(device, a, bt, c, aq, btq, m, n, k,
+                                        max_ctas))
+    return c, aq, btq
+
+
+def gemm_mxfp4_bench(m=8192, n=8192, k=8192, warmup=2, iters=10, device=0):
+    """Returns (ms_per_gemm, tflops) for the MXFP4 kernel (2*M*N*K FLOPs)."""
+    ms = ctypes.c_double()
+    tf = ctypes.c_double()
+    _check(_load().lg_gemm_mxfp4_bench(device, m, n, k, warmup, iters,
+                                       ctypes.byref(ms), ctypes.byref(tf)))
+    return ms.value, tf.value
+
+
 def gemm_burn(target_util_pct: float, seconds: float, device: int = 0,
               m: int = 4096, n: int = 4096, k: int = 4096,
-              period_ms: float = 100.0, fp8: bool = False):
+              period_ms: float = 100.0, fp8: bool = False,
+              fp4: bool = False):
     """Duty-cycled GEMM load at a target GPU-busy percentage (closed-loop
-    on measured GPU-active time); fp8=True burns with the E4M3 kernel."""
-    fn = _load().lg_gemm_fp8_burn if fp8 else _load().lg_gemm_burn
+    on measured GPU-active time); fp8=True burns with the E4M3 kernel,
+    fp4=True with the MXFP4 kernel (not both)."""
+    if fp8 and fp4:
+        raise ValueError("gemm_burn: fp8 and fp4 are mutually exclusive")
+    lib = _load()
+    fn = (lib.lg_gemm_mxfp4_burn if fp4
+          else lib.lg_gemm_fp8_burn if fp8 else lib.lg_gemm_burn)
     _check(fn(device, target_util_pct, seconds, m, n, k, period_ms, None))
 
 

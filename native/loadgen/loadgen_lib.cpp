@@ -10,6 +10,8 @@
 //   * lg_gemm_burn(): duty-cycled MFMA bf16 GEMM bursts targeting a given
 //     GPU-busy percentage — the high/tunable load the scale-up experiments
 //     need (reference has no equivalent).
+//   * lg_gemm_fp8_*/lg_gemm_mxfp4_*(): the same bench/burn/verify entries
+//     over the fp8 (E4M3) and MXFP4 (E2M1 + E8M0 block scale) MFMA kernels.
 //   * lg_*_verify(): run one kernel on caller-provided host data so tests
 //     can check numerics against a plain fp32 reference.
 //
@@ -25,6 +27,8 @@
 #include <cstring>
 #include <thread>
 #include <vector>
+
+#include "mxfp4_host.h"
 
 extern "C" __global__ void vector_add_f32(const float*, const float*, float*, int);
 extern "C" __global__ void vector_add_f32x4(const float4*, const float4*, float4*, int);
@@ -65,6 +69,10 @@ extern "C" __global__ void gemm_fp8_tn_256_db(const unsigned char*,
 extern "C" __global__ void gemm_fp8_tn_256_nr(const unsigned char*,
                                               const unsigned char*, float*, int,
                                               int, int, int);
+extern "C" __global__ void gemm_mxfp4_tn_256(const unsigned char*,
+                                             const unsigned char*, const int*,
+                                             const int*, float*, int, int, int,
+                                             int);
 
 #define LG_CHECK(expr)                                                        \
     do {                                                                      \
@@ -390,7 +398,7 @@ int lg_bw_burn(int device, double target_util_pct, double seconds, double gb,
 // Shared closed-loop duty engine: runs `launch4()` (4 queued kernel
 // launches + sync, hipEvent-measured) in busy bursts of duty*period and
 // trims the duty fraction by the measured GPU-active fraction per actual
-// period. Used by the bf16 and fp8 burn entries.
+// period. Used by the bf16, fp8 and mxfp4 burn entries.
 template <typename LaunchFn>
 static int duty_burn_loop(double target_util_pct, double seconds,
                           double period_ms, volatile int* stop_flag,
@@ -705,3 +713,181 @@ int lg_gemm_fp8_burn(int device, double target_util_pct, double seconds,
 
 } // extern "C"
 
+
+// ---------------------------------------------------------------------------
+// MXFP4 (E2M1 + E8M0 block scale) MFMA GEMM — the CDNA4 4x-peak datatype
+// (gemm_mxfp4_256.hip). Public operand format and quantizer: mxfp4_host.h.
+// ---------------------------------------------------------------------------
+
+struct Mxfp4GemmBufs {
+    unsigned char* a = nullptr;   // [m][k/2]
+    unsigned char* bt = nullptr;  // [n][k/2]
+    int* sa = nullptr;            // [m/64][k/128][64], mxfp4::shuffle_scales
+    int* sb = nullptr;            // [n/64][k/128][64]
+    float* c = nullptr;
+    int m = 0, n = 0, k = 0;
+};
+
+static bool mxfp4_dims_ok(int m, int n, int k)
+{
+    if (m <= 0 || n <= 0 || k <= 0 || m % 256 || n % 256 || k % 256) {
+        std::snprintf(g_last_error, sizeof(g_last_error),
+                      "mxfp4 gemm dims must be positive multiples of "
+                      "256/256/256");
+        return false;
+    }
+    return true;
+}
+
+static int mxfp4_gemm_alloc(Mxfp4GemmBufs& g, int m, int n, int k,
+                            bool fill_random)
+{
+    const size_t na = (size_t)m * k / 2, nb = (size_t)n * k / 2;
+    const size_t nsa = (size_t)m * k / 32, nsb = (size_t)n * k / 32;
+    LG_CHECK(hipMalloc(&g.a, na));
+    LG_CHECK(hipMalloc(&g.bt, nb));
+    LG_CHECK(hipMalloc(&g.sa, nsa));
+    LG_CHECK(hipMalloc(&g.sb, nsb));
+    LG_CHECK(hipMalloc(&g.c, (size_t)m * n * 4));
+    g.m = m; g.n = n; g.k = k;
+    if (fill_random) {
+        // random E2M1 codes (every byte is a valid pair) and scale bytes in
+        // 125..129, never zeros: DVFS-honest load (playbook rule 25)
+        std::vector<unsigned char> h(na > nb ? na : nb);
+        uint32_t st = 0x1357bdf1u;
+        for (size_t i = 0; i < h.size(); ++i) {
+            st = st * 1664525u + 1013904223u;
+            h[i] = (unsigned char)(st >> 16);
+        }
+        LG_CHECK(hipMemcpy(g.a, h.data(), na, hipMemcpyHostToDevice));
+        LG_CHECK(hipMemcpy(g.bt, h.data(), nb, hipMemcpyHostToDevice));
+        h.resize(nsa > nsb ? nsa : nsb);
+        for (size_t i = 0; i < h.size(); ++i) {
+            st = st * 1664525u + 1013904223u;
+            h[i] = (unsigned char)(125 + (st >> 16) % 5);
+        }
+        LG_CHECK(hipMemcpy(g.sa, h.data(), nsa, hipMemcpyHostToDevice));
+        LG_CHECK(hipMemcpy(g.sb, h.data(), nsb, hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+static void mxfp4_gemm_free(Mxfp4GemmBufs& g)
+{
+    (void)hipFree(g.a); (void)hipFree(g.bt); (void)hipFree(g.sa);
+    (void)hipFree(g.sb); (void)hipFree(g.c);
+    g = Mxfp4GemmBufs{};
+}
+
+// max_ctas > 0 caps the grid (each CTA then loops over several tiles).
+static int mxfp4_gemm_launch(const Mxfp4GemmBufs& g, hipStream_t stream,
+                             int max_ctas = 0)
+{
+    int n_tiles = (g.m / 256) * (g.n / 256);
+    int blocks = n_tiles < 2048 ? n_tiles : 2048;
+    if (max_ctas > 0 && blocks > max_ctas) blocks = max_ctas;
+    int tiles_per_cta = (n_tiles + blocks - 1) / blocks;
+    hipLaunchKernelGGL(gemm_mxfp4_tn_256, dim3(blocks), dim3(512), 0, stream,
+                       g.a, g.bt, g.sa, g.sb, g.c, g.m, g.n, g.k,
+                       tiles_per_cta);
+    return 0;
+}
+
+// Quantize one f32 operand, upload elements + device-layout scales, and
+// hand back the dequantized values.
+static int mxfp4_upload_operand(const float* x_h, int rows, int k,
+                                unsigned char* elems_d, int* scales_d,
+                                float* deq_out)
+{
+    std::vector<unsigned char> packed((size_t)rows * k / 2);
+    std::vector<unsigned char> scales((size_t)rows * k / 32);
+    if (mxfp4::quantize(x_h, rows, k, packed.data(), scales.data(), deq_out,
+                        g_last_error, sizeof(g_last_error)))
+        return -1;
+    std::vector<unsigned char> shuffled(scales.size());
+    mxfp4::shuffle_scales(scales.data(), rows, k, shuffled.data());
+    LG_CHECK(hipMemcpy(elems_d, packed.data(), packed.size(),
+                       hipMemcpyHostToDevice));
+    LG_CHECK(hipMemcpy(scales_d, shuffled.data(), shuffled.size(),
+                       hipMemcpyHostToDevice));
+    return 0;
+}
+
+extern "C" {
+
+// Timed MXFP4 GEMM: mean ms + TF/s (2*M*N*K) over `iters` launches.
+int lg_gemm_mxfp4_bench(int device, int m, int n, int k, int warmup, int iters,
+                        double* ms_out, double* tflops_out)
+{
+    if (!mxfp4_dims_ok(m, n, k)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    Mxfp4GemmBufs g;
+    if (mxfp4_gemm_alloc(g, m, n, k, true)) return -1;
+    for (int i = 0; i < warmup; ++i) mxfp4_gemm_launch(g, 0);
+    LG_CHECK(hipDeviceSynchronize());
+    double t0 = now_ms();
+    for (int i = 0; i < iters; ++i) mxfp4_gemm_launch(g, 0);
+    LG_CHECK(hipDeviceSynchronize());
+    double t1 = now_ms();
+    double ms = (t1 - t0) / iters;
+    if (ms_out) *ms_out = ms;
+    if (tflops_out) *tflops_out = 2.0 * m * n * k / (ms * 1e-3) / 1e12;
+    mxfp4_gemm_free(g);
+    return 0;
+}
+
+// Numerics entry: quantizes the f32 inputs to MXFP4 with the shared host
+// quantizer, runs the kernel, and writes C plus the DEQUANTIZED inputs
+// (aq/btq, f32) back so the caller can compute the exact reference on what
+// the GPU actually multiplied. max_ctas > 0 caps the grid so a small shape
+// exercises the tiles-per-CTA loop; 0 = the normal grid.
+int lg_gemm_mxfp4_verify(int device, const float* a_h, const float* bt_h,
+                         float* c_out, float* aq_out, float* btq_out,
+                         int m, int n, int k, int max_ctas)
+{
+    if (!mxfp4_dims_ok(m, n, k)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    Mxfp4GemmBufs g;
+    if (mxfp4_gemm_alloc(g, m, n, k, false)) return -1;
+    int rc = mxfp4_upload_operand(a_h, m, k, g.a, g.sa, aq_out);
+    if (!rc) rc = mxfp4_upload_operand(bt_h, n, k, g.bt, g.sb, btq_out);
+    if (rc) {
+        mxfp4_gemm_free(g);
+        return -1;
+    }
+    mxfp4_gemm_launch(g, 0, max_ctas);
+    LG_CHECK(hipDeviceSynchronize());
+    LG_CHECK(hipGetLastError());
+    LG_CHECK(hipMemcpy(c_out, g.c, (size_t)m * n * 4, hipMemcpyDeviceToHost));
+    mxfp4_gemm_free(g);
+    return 0;
+}
+
+// MXFP4 variant of the burn: same closed-loop duty engine over the
+// block-scaled fp4 MFMA kernel — the load shape of an MXFP4 serving pod.
+int lg_gemm_mxfp4_burn(int device, double target_util_pct, double seconds,
+                       int m, int n, int k, double period_ms,
+                       volatile int* stop_flag)
+{
+    if (m <= 0) m = 4096;
+    if (n <= 0) n = 4096;
+    if (k <= 0) k = 4096;
+    if (period_ms <= 0) period_ms = 100.0;
+    if (!mxfp4_dims_ok(m, n, k)) return -1;
+    if (target_util_pct < 0) target_util_pct = 0;
+    if (target_util_pct > 100) target_util_pct = 100;
+    LG_CHECK(hipSetDevice(device));
+    Mxfp4GemmBufs g;
+    if (mxfp4_gemm_alloc(g, m, n, k, true)) return -1;
+    mxfp4_gemm_launch(g, 0);
+    LG_CHECK(hipDeviceSynchronize());
+    int rc = duty_burn_loop(target_util_pct, seconds, period_ms, stop_flag,
+                            [&] {
+                                for (int b = 0; b < 4; ++b)
+                                    mxfp4_gemm_launch(g, 0);
+                            });
+    mxfp4_gemm_free(g);
+    return rc;
+}
+
+} // extern "C"

@@ -8,8 +8,13 @@
 //       the reference's load shape: tiny kernel, launch-bound, a few % util
 //   mi355x-loadgen gemm [--m/--n-dim/--k 4096] [--iters 50] [--device 0]
 //       one timed MFMA bf16 GEMM burst; prints ms + TFLOP/s
-//   mi355x-loadgen burn --util 80 [--seconds 60] [--device 0]
-//       duty-cycled GEMM load at a target busy%% (tunable HPA-test load)
+//   mi355x-loadgen fp8gemm [--m/--n-dim/--k 8192] [--iters 10] [--no-raster]
+//       one timed fp8 (E4M3) MFMA GEMM burst
+//   mi355x-loadgen fp4gemm [--m/--n-dim/--k 8192] [--iters 10]
+//       one timed MXFP4 (E2M1 + E8M0 block scale) MFMA GEMM burst
+//   mi355x-loadgen burn --util 80 [--seconds 60] [--device 0] [--fp8|--fp4]
+//       duty-cycled GEMM load at a target busy%% (tunable HPA-test load);
+//       --fp8 / --fp4 burn with the E4M3 / MXFP4 kernel instead of bf16
 //
 // Exit code 0 on success, 1 on usage error, 2 on HIP error.
 
@@ -29,8 +34,13 @@ int lg_gemm_bf16_bench_variant(int device, int m, int n, int k, int warmup,
                                double* tflops_out);
 int lg_gemm_fp8_bench(int device, int m, int n, int k, int warmup, int iters,
                       int raster, double* ms_out, double* tflops_out);
+int lg_gemm_mxfp4_bench(int device, int m, int n, int k, int warmup, int iters,
+                        double* ms_out, double* tflops_out);
 int lg_gemm_burn(int device, double target_util_pct, double seconds,
                  int m, int n, int k, double period_ms, volatile int* stop_flag);
+int lg_gemm_mxfp4_burn(int device, double target_util_pct, double seconds,
+                       int m, int n, int k, double period_ms,
+                       volatile int* stop_flag);
 int lg_gemm_fp8_burn(int device, double target_util_pct, double seconds,
                      int m, int n, int k, double period_ms,
                      volatile int* stop_flag);
@@ -49,7 +59,7 @@ int main(int argc, char** argv)
 {
     if (argc < 2) {
         std::fprintf(stderr,
-                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|burn|bwburn|devices} [flags]\n");
+                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|fp4gemm|burn|bwburn|devices} [flags]\n");
         return 1;
     }
     std::string mode = argv[1];
@@ -115,6 +125,21 @@ int main(int argc, char** argv)
         std::printf("gemm_fp8 %dx%dx%d ms=%.3f tflops=%.1f\n", m, n, k, ms, tf);
         return 0;
     }
+    if (mode == "fp4gemm") {
+        int m = (int)argd(argc, argv, "--m", 8192);
+        int n = (int)argd(argc, argv, "--n-dim", 8192);
+        int k = (int)argd(argc, argv, "--k", 8192);
+        int iters = (int)argd(argc, argv, "--iters", 10);
+        int warmup = (int)argd(argc, argv, "--warmup", 2);
+        double ms = 0, tf = 0;
+        if (lg_gemm_mxfp4_bench(device, m, n, k, warmup, iters, &ms, &tf)) {
+            std::fprintf(stderr, "error: %s\n", lg_last_error());
+            return 2;
+        }
+        std::printf("gemm_mxfp4 %dx%dx%d ms=%.3f tflops=%.1f\n", m, n, k, ms,
+                    tf);
+        return 0;
+    }
     if (mode == "burn") {
         double util = argd(argc, argv, "--util", 80.0);
         double seconds = argd(argc, argv, "--seconds", 60.0);
@@ -122,13 +147,21 @@ int main(int argc, char** argv)
         int n = (int)argd(argc, argv, "--n-dim", 4096);
         int k = (int)argd(argc, argv, "--k", 4096);
         double period = argd(argc, argv, "--period-ms", 100.0);
-        bool fp8 = false;
-        for (int i = 1; i < argc; ++i)
+        bool fp8 = false, fp4 = false;
+        for (int i = 1; i < argc; ++i) {
             if (!std::strcmp(argv[i], "--fp8")) fp8 = true;
-        int rc = fp8 ? lg_gemm_fp8_burn(device, util, seconds, m, n, k,
-                                        period, nullptr)
-                     : lg_gemm_burn(device, util, seconds, m, n, k, period,
-                                    nullptr);
+            if (!std::strcmp(argv[i], "--fp4")) fp4 = true;
+        }
+        if (fp8 && fp4) {
+            std::fprintf(stderr, "burn: --fp8 and --fp4 are exclusive\n");
+            return 1;
+        }
+        int rc = fp4   ? lg_gemm_mxfp4_burn(device, util, seconds, m, n, k,
+                                            period, nullptr)
+                 : fp8 ? lg_gemm_fp8_burn(device, util, seconds, m, n, k,
+                                          period, nullptr)
+                       : lg_gemm_burn(device, util, seconds, m, n, k, period,
+                                      nullptr);
         if (rc) {
             std::fprintf(stderr, "error: %s\n", lg_last_error());
             return 2;
