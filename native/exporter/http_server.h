@@ -7,8 +7,12 @@
 //   GET /healthz  -> 200 once the process is up (liveness)
 //   GET /readyz   -> 200 after the first successful counter sample
 //                    (readiness), 503 before
-// Single accept thread + short-lived handler threads; Prometheus scrapes at
-// 1 s (kube-prometheus-stack-values.yaml:5) are trivially sustained.
+// One thread runs one poll() loop over the listen socket and the open
+// connections. Connections are persistent (HTTP/1.1 keep-alive), the way
+// Prometheus scrapes: at 1 s (kube-prometheus-stack-values.yaml:5) a scrape
+// costs no connect/accept/close. Sockets are non-blocking, so a silent or
+// slow client never delays another connection: a partial send waits for
+// POLLOUT as pending output.
 
 #pragma once
 
@@ -33,9 +37,22 @@ class HttpServer {
     void stop();
     int bound_port() const { return port_; }
 
+    // At most this many connections stay open; when one more is accepted,
+    // the longest-idle one is closed.
+    static constexpr int kMaxConnections = 64;
+    // A connection with no traffic for this long is closed. Longer than
+    // the 1 s to 15 s scrape intervals in use, so a Prometheus keeps its
+    // connection from one scrape to the next.
+    static constexpr int kIdleTimeoutS = 60;
+
   private:
-    void accept_loop();
-    void handle(int fd);
+    struct Conn;
+    void serve_loop();
+    bool service(Conn& c, short revents);
+    static bool answerable(const Conn& c);
+    void answer_buffered(Conn& c);
+    bool flush(Conn& c);
+    void respond(Conn& c, const std::string& req);
 
     std::string bind_addr_;
     int port_;
