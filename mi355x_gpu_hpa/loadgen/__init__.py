@@ -1,7 +1,7 @@
 """ctypes bindings for the CDNA4 HIP load-generator library.
 
 Native side: native/loadgen/{vector_add,gemm_bf16,gemm_fp8_256,
-gemm_mxfp4_256}.hip + loadgen_lib.cpp, built by ``make -C native loadgen``
+gemm_mxfp4_256,gemm_mxfp4_decode}.hip + loadgen_lib.cpp, built by ``make -C native loadgen``
 into native/build/libmi355x_loadgen.so. The MXFP4 quantizer is also built
 on its own, without HIP, into native/build/libmi355x_mxfp4.so.
 
@@ -112,6 +112,19 @@ def _load():
         lib.lg_gemm_mxfp4_verify.argtypes = (
             lib.lg_gemm_fp8_verify.argtypes + [ctypes.c_int]
         )
+        lib.lg_decode_mxfp4_verify.argtypes = (
+            lib.lg_gemm_fp8_verify.argtypes + [ctypes.c_int, ctypes.c_int]
+        )
+        lib.lg_decode_mxfp4_bench.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.lg_decode_mxfp4_burn.argtypes = [
+            ctypes.c_int, ctypes.c_double, ctypes.c_double,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_double, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+        ]
         lib.lg_bw_burn.argtypes = [
             ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
             ctypes.c_double, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
@@ -295,6 +308,60 @@ def gemm_burn(target_util_pct: float, seconds: float, device: int = 0,
     fn = (lib.lg_gemm_mxfp4_burn if fp4
           else lib.lg_gemm_fp8_burn if fp8 else lib.lg_gemm_burn)
     _check(fn(device, target_util_pct, seconds, m, n, k, period_ms, None))
+
+
+def decode_mxfp4(x: np.ndarray, w: np.ndarray, device: int = 0,
+                 k_splits: int = 0):
+    """Decode-phase MXFP4 weight-streaming GEMM numerics entry: x f32
+    [m, k] with 1 <= m <= 64, w f32 [n, k] (one layer) or [layers, n, k];
+    n % 64 == 0, k % 128 == 0. Both are quantized like mxfp4_quantize();
+    returns (c, xq, wq) with c[..., m, n] = xq @ wq[layer].T per layer and
+    xq/wq the dequantized (f32) operands the GPU actually multiplied.
+    k_splits: 0 = the library's heuristic, > 0 forces that many K slices
+    across CTAs (must divide k/128)."""
+    x = np.ascontiguousarray(x, np.float32)
+    w = np.ascontiguousarray(w, np.float32)
+    if x.ndim != 2 or w.ndim not in (2, 3) or x.shape[1] != w.shape[-1]:
+        raise LoadgenError("decode_mxfp4 expects x [m, k] and w [n, k] or "
+                           "[layers, n, k]")
+    m, k = x.shape
+    w3 = w.reshape((-1,) + w.shape[-2:])
+    layers, n, _ = w3.shape
+    c = np.empty((layers, m, n), np.float32)
+    xq = np.empty_like(x)
+    wq = np.empty_like(w3)
+    _check(_load().lg_decode_mxfp4_verify(device, x, w3, c, xq, wq, m, n, k,
+                                          layers, k_splits))
+    if w.ndim == 2:
+        return c[0], xq, wq[0]
+    return c, xq, wq
+
+
+def decode_mxfp4_bench(m=16, n=8192, k=8192, layers=16, warmup=2, iters=10,
+                       device=0):
+    """Returns (ms_per_step, weight_gbps): one step is a pass over the ring
+    of `layers` weight matrices; weight_gbps counts the weight elements and
+    scales streamed per step."""
+    ms = ctypes.c_double()
+    gbps = ctypes.c_double()
+    _check(_load().lg_decode_mxfp4_bench(device, m, n, k, layers, warmup,
+                                         iters, ctypes.byref(ms),
+                                         ctypes.byref(gbps)))
+    return ms.value, gbps.value
+
+
+def decode_burn(target_util_pct: float, seconds: float, device: int = 0,
+                batch: int = 16, n: int = 8192, k: int = 8192,
+                layers: int = 16, period_ms: float = 100.0) -> float:
+    """Duty-cycled decode load at a target GPU-busy percentage (the shared
+    closed-loop duty engine over decode steps): the busy-but-bandwidth-bound
+    shape of a small-batch MXFP4 serving pod. Returns the weight GB/s
+    streamed during the busy bursts."""
+    gbps = ctypes.c_double()
+    _check(_load().lg_decode_mxfp4_burn(device, target_util_pct, seconds,
+                                        batch, n, k, layers, period_ms, None,
+                                        ctypes.byref(gbps)))
+    return gbps.value
 
 
 def bw_burn(target_util_pct: float, seconds: float, device: int = 0,

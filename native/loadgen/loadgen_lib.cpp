@@ -12,6 +12,9 @@
 //     need (reference has no equivalent).
 //   * lg_gemm_fp8_*/lg_gemm_mxfp4_*(): the same bench/burn/verify entries
 //     over the fp8 (E4M3) and MXFP4 (E2M1 + E8M0 block scale) MFMA kernels.
+//   * lg_decode_mxfp4_*(): the decode half of an inference pod — a skinny-M
+//     (1..64 rows) MXFP4 GEMM streaming a ring of weight matrices from HBM
+//     (gemm_mxfp4_decode.hip): busy% high, matrix cores idle, bandwidth-bound.
 //   * lg_*_verify(): run one kernel on caller-provided host data so tests
 //     can check numerics against a plain fp32 reference.
 //
@@ -73,6 +76,17 @@ extern "C" __global__ void gemm_mxfp4_tn_256(const unsigned char*,
                                              const unsigned char*, const int*,
                                              const int*, float*, int, int, int,
                                              int);
+#define LG_DECODE_KERNEL(NAME)                                                \
+    extern "C" __global__ void NAME(const unsigned char*, const int*,        \
+                                    const unsigned char*, const int*, float*, \
+                                    int, int, int, int, int)
+LG_DECODE_KERNEL(decode_mxfp4_m16);
+LG_DECODE_KERNEL(decode_mxfp4_m32);
+LG_DECODE_KERNEL(decode_mxfp4_m48);
+LG_DECODE_KERNEL(decode_mxfp4_m64);
+#undef LG_DECODE_KERNEL
+extern "C" __global__ void decode_mxfp4_reduce(const float4*, float4*, long,
+                                               int);
 
 #define LG_CHECK(expr)                                                        \
     do {                                                                      \
@@ -887,6 +901,305 @@ int lg_gemm_mxfp4_burn(int device, double target_util_pct, double seconds,
                                     mxfp4_gemm_launch(g, 0);
                             });
     mxfp4_gemm_free(g);
+    return rc;
+}
+
+} // extern "C"
+
+
+// ---------------------------------------------------------------------------
+// Decode-phase MXFP4 weight streaming (gemm_mxfp4_decode.hip): a skinny-M
+// a4w4 GEMM over a ring of `layers` weight matrices W[L][N][K] and one
+// activation block X[M][K], 1 <= M <= 64. Memory-bound by design: each
+// weight byte is read once per step.
+// ---------------------------------------------------------------------------
+
+struct DecodeBufs {
+    unsigned char* x = nullptr;  // [mp][k/2], mp = m rounded up to 16
+    int* sx = nullptr;           // [k/128][64], one 64-row group
+    unsigned char* w = nullptr;  // [layers][n][k/2]
+    int* sw = nullptr;           // [layers*n/64][k/128][64]
+    float* c = nullptr;          // [layers][m][n]
+    float* part = nullptr;       // [k_splits][layers][m][n] if k_splits > 1
+    int m = 0, mp = 0, n = 0, k = 0, layers = 0, k_splits = 1;
+};
+
+static bool decode_dims_ok(int m, int n, int k, int layers, int k_splits)
+{
+    if (m < 1 || m > 64 || n <= 0 || n % 64 || k <= 0 || k % 128 ||
+        layers < 1) {
+        std::snprintf(g_last_error, sizeof(g_last_error),
+                      "mxfp4 decode needs 1 <= m <= 64, n a positive "
+                      "multiple of 64, k of 128, layers >= 1");
+        return false;
+    }
+    if (k_splits < 0 || (k_splits > 0 && (k / 128) % k_splits)) {
+        std::snprintf(g_last_error, sizeof(g_last_error),
+                      "mxfp4 decode: k_splits %d must divide k/128 = %d",
+                      k_splits, k / 128);
+        return false;
+    }
+    return true;
+}
+
+// Product heuristic: a CTA is one (layer, 64-row group, K slice). Split K
+// across CTAs until the grid reaches two CTAs per CU (the chip has 256),
+// as long as a slice keeps at least 8 k-steps (two per wave).
+static int decode_pick_k_splits(int n, int k, int layers)
+{
+    const long ctas = (long)layers * (n / 64);
+    const int ksteps = k / 128;
+    int s = 1;
+    while (ctas * s < 512 && ksteps % (s * 2) == 0 && ksteps / (s * 2) >= 8)
+        s *= 2;
+    return s;
+}
+
+static void decode_free(DecodeBufs& d)
+{
+    (void)hipFree(d.x); (void)hipFree(d.sx); (void)hipFree(d.w);
+    (void)hipFree(d.sw); (void)hipFree(d.c); (void)hipFree(d.part);
+    d = DecodeBufs{};
+}
+
+// k_splits: 0 = heuristic. Dimensions must have passed decode_dims_ok.
+static int decode_alloc(DecodeBufs& d, int m, int n, int k, int layers,
+                        int k_splits)
+{
+    d.m = m; d.mp = (m + 15) / 16 * 16; d.n = n; d.k = k; d.layers = layers;
+    d.k_splits = k_splits > 0 ? k_splits : decode_pick_k_splits(n, k, layers);
+    const size_t c_bytes = (size_t)layers * m * n * 4;
+    LG_CHECK(hipMalloc(&d.x, (size_t)d.mp * k / 2));
+    LG_CHECK(hipMalloc(&d.sx, (size_t)64 * k / 32));
+    LG_CHECK(hipMalloc(&d.w, (size_t)layers * n * k / 2));
+    LG_CHECK(hipMalloc(&d.sw, (size_t)layers * n * k / 32));
+    LG_CHECK(hipMalloc(&d.c, c_bytes));
+    if (d.k_splits > 1) LG_CHECK(hipMalloc(&d.part, c_bytes * d.k_splits));
+    return 0;
+}
+
+// One decode step: every layer of the ring against X. One launch for the
+// ring, plus the ordered slice sum when K is split across CTAs. Verify,
+// bench and burn all run this function.
+static void decode_step(const DecodeBufs& d, hipStream_t stream)
+{
+    const int blocks = d.layers * (d.n / 64) * d.k_splits;
+    float* out = d.k_splits > 1 ? d.part : d.c;
+    auto kern = d.mp == 16   ? decode_mxfp4_m16
+                : d.mp == 32 ? decode_mxfp4_m32
+                : d.mp == 48 ? decode_mxfp4_m48
+                             : decode_mxfp4_m64;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, stream, d.x, d.sx,
+                       d.w, d.sw, out, d.m, d.n, d.k, d.layers, d.k_splits);
+    if (d.k_splits > 1) {
+        const long n4 = (long)d.layers * d.m * d.n / 4;
+        long rb = (n4 + 255) / 256;
+        if (rb > 2048) rb = 2048;
+        hipLaunchKernelGGL(decode_mxfp4_reduce, dim3((int)rb), dim3(256), 0,
+                           stream, (const float4*)d.part, (float4*)d.c, n4,
+                           d.k_splits);
+    }
+}
+
+static double decode_weight_bytes(const DecodeBufs& d)
+{
+    return (double)d.layers * ((double)d.n * d.k / 2 + (double)d.n * d.k / 32);
+}
+
+// Random codes and scale bytes 125..129 (DVFS-honest, as mxfp4_gemm_alloc).
+// One layer is generated on the host and replicated on the device.
+static int decode_fill_random(DecodeBufs& d)
+{
+    const size_t wl = (size_t)d.n * d.k / 2, swl = (size_t)d.n * d.k / 32;
+    const size_t xb = (size_t)d.mp * d.k / 2, sxb = (size_t)64 * d.k / 32;
+    std::vector<unsigned char> h(wl > xb ? wl : xb);
+    uint32_t st = 0x0decade1u;
+    for (size_t i = 0; i < h.size(); ++i) {
+        st = st * 1664525u + 1013904223u;
+        h[i] = (unsigned char)(st >> 16);
+    }
+    LG_CHECK(hipMemcpy(d.w, h.data(), wl, hipMemcpyHostToDevice));
+    LG_CHECK(hipMemcpy(d.x, h.data(), xb, hipMemcpyHostToDevice));
+    h.resize(swl > sxb ? swl : sxb);
+    for (size_t i = 0; i < h.size(); ++i) {
+        st = st * 1664525u + 1013904223u;
+        h[i] = (unsigned char)(125 + (st >> 16) % 5);
+    }
+    LG_CHECK(hipMemcpy(d.sw, h.data(), swl, hipMemcpyHostToDevice));
+    LG_CHECK(hipMemcpy(d.sx, h.data(), sxb, hipMemcpyHostToDevice));
+    for (int l = 1; l < d.layers; ++l) {
+        LG_CHECK(hipMemcpy(d.w + l * wl, d.w, wl, hipMemcpyDeviceToDevice));
+        LG_CHECK(hipMemcpy((unsigned char*)d.sw + l * swl, d.sw, swl,
+                           hipMemcpyDeviceToDevice));
+    }
+    return 0;
+}
+
+static void decode_defaults(int& m, int& n, int& k, int& layers)
+{
+    if (m <= 0) m = 16;
+    if (n <= 0) n = 8192;
+    if (k <= 0) k = 8192;
+    if (layers <= 0) layers = 16;
+}
+
+extern "C" {
+
+// Numerics entry: x_h[m][k] and w_h[layers][n][k] (f32) are quantized with
+// the shared host quantizer; writes c_out[layers][m][n] and the
+// DEQUANTIZED operands xq_out/wq_out (same convention as
+// lg_gemm_mxfp4_verify). k_splits: 0 = the product heuristic, > 0 forces
+// that many K slices across CTAs (must divide k/128) so a small shape
+// reaches every combine path.
+int lg_decode_mxfp4_verify(int device, const float* x_h, const float* w_h,
+                           float* c_out, float* xq_out, float* wq_out, int m,
+                           int n, int k, int layers, int k_splits)
+{
+    if (!decode_dims_ok(m, n, k, layers, k_splits)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    const long wrows = (long)layers * n;
+    const int kb = k / 32;
+    // X: elements padded to mp rows with zero codes, scales to one 64-row
+    // group with byte 127
+    const int mp = (m + 15) / 16 * 16;
+    std::vector<unsigned char> xe((size_t)mp * k / 2, 0);
+    std::vector<unsigned char> xs((size_t)64 * kb, 127);
+    std::vector<unsigned char> xsh(xs.size());
+    if (mxfp4::quantize(x_h, m, k, xe.data(), xs.data(), xq_out, g_last_error,
+                        sizeof(g_last_error)))
+        return -1;
+    mxfp4::shuffle_scales(xs.data(), 64, k, xsh.data());
+    std::vector<unsigned char> we((size_t)wrows * k / 2);
+    std::vector<unsigned char> ws((size_t)wrows * kb);
+    std::vector<unsigned char> wsh(ws.size());
+    if (mxfp4::quantize(w_h, wrows, k, we.data(), ws.data(), wq_out,
+                        g_last_error, sizeof(g_last_error)))
+        return -1;
+    mxfp4::shuffle_scales(ws.data(), (int)wrows, k, wsh.data());
+
+    DecodeBufs d;
+    int rc = decode_alloc(d, m, n, k, layers, k_splits);
+    auto up = [&](void* dst, const std::vector<unsigned char>& src) {
+        LG_CHECK(hipMemcpy(dst, src.data(), src.size(), hipMemcpyHostToDevice));
+        return 0;
+    };
+    if (!rc) rc = up(d.x, xe);
+    if (!rc) rc = up(d.sx, xsh);
+    if (!rc) rc = up(d.w, we);
+    if (!rc) rc = up(d.sw, wsh);
+    auto run = [&] {
+        decode_step(d, 0);
+        LG_CHECK(hipDeviceSynchronize());
+        LG_CHECK(hipGetLastError());
+        LG_CHECK(hipMemcpy(c_out, d.c, (size_t)layers * m * n * 4,
+                           hipMemcpyDeviceToHost));
+        return 0;
+    };
+    if (!rc) rc = run();
+    decode_free(d);
+    return rc;
+}
+
+// Timed decode steps: mean ms per step (one pass over the ring) and the
+// weight stream rate, layers * (N*K/2 + N*K/32) bytes / step time, GB/s.
+int lg_decode_mxfp4_bench(int device, int m, int n, int k, int layers,
+                          int warmup, int iters, double* ms_per_step_out,
+                          double* weight_gbps_out)
+{
+    decode_defaults(m, n, k, layers);
+    if (iters < 1) iters = 1;
+    if (!decode_dims_ok(m, n, k, layers, 0)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    DecodeBufs d;
+    auto run = [&] {
+        if (decode_alloc(d, m, n, k, layers, 0)) return -1;
+        if (decode_fill_random(d)) return -1;
+        for (int i = 0; i < warmup; ++i) decode_step(d, 0);
+        LG_CHECK(hipDeviceSynchronize());
+        double t0 = now_ms();
+        for (int i = 0; i < iters; ++i) decode_step(d, 0);
+        LG_CHECK(hipDeviceSynchronize());
+        double ms = (now_ms() - t0) / iters;
+        LG_CHECK(hipGetLastError());
+        if (ms_per_step_out) *ms_per_step_out = ms;
+        if (weight_gbps_out)
+            *weight_gbps_out = decode_weight_bytes(d) / (ms * 1e-3) / 1e9;
+        return 0;
+    };
+    int rc = run();
+    decode_free(d);
+    return rc;
+}
+
+// Decode burn: the shared closed-loop duty engine over decode steps — the
+// load shape of a small-batch MXFP4 serving pod (busy%, bandwidth-bound).
+// *weight_gbps_out: weight bytes streamed / GPU-active time of the bursts.
+int lg_decode_mxfp4_burn(int device, double target_util_pct, double seconds,
+                         int m, int n, int k, int layers, double period_ms,
+                         volatile int* stop_flag, double* weight_gbps_out)
+{
+    decode_defaults(m, n, k, layers);
+    if (period_ms <= 0) period_ms = 100.0;
+    if (!decode_dims_ok(m, n, k, layers, 0)) return -1;
+    if (target_util_pct < 0) target_util_pct = 0;
+    if (target_util_pct > 100) target_util_pct = 100;
+    LG_CHECK(hipSetDevice(device));
+    DecodeBufs d;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double active_ms = 0, steps = 0;
+    auto run = [&] {
+        if (decode_alloc(d, m, n, k, layers, 0)) return -1;
+        if (decode_fill_random(d)) return -1;
+        LG_CHECK(hipEventCreate(&e0));
+        LG_CHECK(hipEventCreate(&e1));
+        // calibration step: sizes the burst so that a busy slice of the
+        // default 100 ms period holds several launches
+        LG_CHECK(hipEventRecord(e0, 0));
+        decode_step(d, 0);
+        LG_CHECK(hipEventRecord(e1, 0));
+        LG_CHECK(hipDeviceSynchronize());
+        float step_ms = 0;
+        LG_CHECK(hipEventElapsedTime(&step_ms, e0, e1));
+        int per_burst = step_ms > 0 ? (int)(2.0f / step_ms) : 4;
+        if (per_burst < 4) per_burst = 4;
+        if (per_burst > 64) per_burst = 64;
+        // rate: each burst is bracketed by events of its own, read back
+        // at the next burst (the engine has synchronised by then), so the
+        // engine itself stays as it is
+        bool pending = false;
+        int rc = duty_burn_loop(
+            target_util_pct, seconds, period_ms, stop_flag, [&] {
+                float dt = 0;
+                if (pending &&
+                    hipEventElapsedTime(&dt, e0, e1) == hipSuccess) {
+                    active_ms += dt;
+                    steps += per_burst;
+                }
+                (void)hipEventRecord(e0, 0);
+                for (int b = 0; b < per_burst; ++b) decode_step(d, 0);
+                (void)hipEventRecord(e1, 0);
+                pending = true;
+            });
+        if (rc) return rc;
+        LG_CHECK(hipDeviceSynchronize());
+        if (pending) {
+            float dt = 0;
+            LG_CHECK(hipEventElapsedTime(&dt, e0, e1));
+            active_ms += dt;
+            steps += per_burst;
+        }
+        LG_CHECK(hipGetLastError());
+        return 0;
+    };
+    int rc = run();
+    if (weight_gbps_out)
+        *weight_gbps_out =
+            active_ms > 0
+                ? steps * decode_weight_bytes(d) / (active_ms * 1e-3) / 1e9
+                : 0;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    decode_free(d);
     return rc;
 }
 

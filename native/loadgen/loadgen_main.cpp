@@ -15,6 +15,16 @@
 //   mi355x-loadgen burn --util 80 [--seconds 60] [--device 0] [--fp8|--fp4]
 //       duty-cycled GEMM load at a target busy%% (tunable HPA-test load);
 //       --fp8 / --fp4 burn with the E4M3 / MXFP4 kernel instead of bf16
+//   mi355x-loadgen decode [--batch 16] [--n-dim 8192] [--k 8192]
+//                         [--layers 16] [--iters 10]
+//       timed decode steps: a skinny-M MXFP4 GEMM streaming a ring of
+//       weight matrices; prints ms per step, weight GB/s, ring footprint
+//   mi355x-loadgen decodeburn --util 80 [--seconds 60] [--batch 16]
+//                         [--n-dim 8192] [--k 8192] [--layers 16]
+//       duty-cycled decode load (busy%% high, HBM-bandwidth-bound): the
+//       load shape of a small-batch MXFP4 serving pod
+//   mi355x-loadgen bwburn --util 80 [--seconds 60] [--gb 6]
+//       duty-cycled streaming-triad HBM load
 //
 // Exit code 0 on success, 1 on usage error, 2 on HIP error.
 
@@ -44,6 +54,12 @@ int lg_gemm_mxfp4_burn(int device, double target_util_pct, double seconds,
 int lg_gemm_fp8_burn(int device, double target_util_pct, double seconds,
                      int m, int n, int k, double period_ms,
                      volatile int* stop_flag);
+int lg_decode_mxfp4_bench(int device, int m, int n, int k, int layers,
+                          int warmup, int iters, double* ms_per_step_out,
+                          double* weight_gbps_out);
+int lg_decode_mxfp4_burn(int device, double target_util_pct, double seconds,
+                         int m, int n, int k, int layers, double period_ms,
+                         volatile int* stop_flag, double* weight_gbps_out);
 int lg_bw_burn(int device, double target_util_pct, double seconds, double gb,
                double period_ms, volatile int* stop_flag, double* gbps_out);
 }
@@ -59,7 +75,7 @@ int main(int argc, char** argv)
 {
     if (argc < 2) {
         std::fprintf(stderr,
-                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|fp4gemm|burn|bwburn|devices} [flags]\n");
+                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|fp4gemm|burn|decode|decodeburn|bwburn|devices} [flags]\n");
         return 1;
     }
     std::string mode = argv[1];
@@ -166,6 +182,47 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "error: %s\n", lg_last_error());
             return 2;
         }
+        return 0;
+    }
+    if (mode == "decode" || mode == "decodeburn") {
+        int m = (int)argd(argc, argv, "--batch", 16);
+        int n = (int)argd(argc, argv, "--n-dim", 8192);
+        int k = (int)argd(argc, argv, "--k", 8192);
+        int layers = (int)argd(argc, argv, "--layers", 16);
+        double ms = 0, gbps = 0;
+        int rc;
+        if (mode == "decode") {
+            int iters = (int)argd(argc, argv, "--iters", 10);
+            int warmup = (int)argd(argc, argv, "--warmup", 2);
+            rc = lg_decode_mxfp4_bench(device, m, n, k, layers, warmup, iters,
+                                       &ms, &gbps);
+        } else {
+            double util = argd(argc, argv, "--util", 80.0);
+            double seconds = argd(argc, argv, "--seconds", 60.0);
+            double period = argd(argc, argv, "--period-ms", 100.0);
+            rc = lg_decode_mxfp4_burn(device, util, seconds, m, n, k, layers,
+                                      period, nullptr, &gbps);
+        }
+        if (rc) {
+            std::fprintf(stderr, "error: %s\n", lg_last_error());
+            return 2;
+        }
+        const double ring_mib =
+            (double)layers * ((double)n * k / 2 + (double)n * k / 32) /
+            (1 << 20);
+        if (mode == "decode")
+            std::printf("decode_mxfp4 batch=%d %dx%d layers=%d ms_per_step=%.3f "
+                        "weight_gbps=%.0f ring_mib=%.0f\n",
+                        m, n, k, layers, ms, gbps, ring_mib);
+        else
+            std::printf("decodeburn batch=%d %dx%d layers=%d weight_gbps=%.0f "
+                        "during bursts ring_mib=%.0f\n",
+                        m, n, k, layers, gbps, ring_mib);
+        if (ring_mib < 512)
+            std::printf("note: a %.0f MiB ring is below 512 MiB and stays in "
+                        "the 256 MiB Infinity Cache in part or whole; this is "
+                        "not an HBM reading\n",
+                        ring_mib);
         return 0;
     }
     if (mode == "bwburn") {

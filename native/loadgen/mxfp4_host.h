@@ -17,8 +17,9 @@
 //   rounds to zero is stored as code 0 (never the negative-zero code 8).
 //   Non-finite input is an error, not an encoding.
 //
-// The device-side scale layout (shuffle_scales) is private to the kernel in
-// gemm_mxfp4_256.hip and may change; the public format does not.
+// The device-side scale layout (shuffle_scales) is private to the kernels in
+// gemm_mxfp4_256.hip and gemm_mxfp4_decode.hip and may change; the public
+// format does not.
 
 #ifndef MI355X_MXFP4_HOST_H
 #define MI355X_MXFP4_HOST_H
@@ -133,7 +134,8 @@ inline void dequantize(const unsigned char* packed, const unsigned char* scales,
     }
 }
 
-// Device scale layout for gemm_mxfp4_tn_256 (rows % 64 == 0, k % 128 == 0):
+// Device scale layout for gemm_mxfp4_tn_256 and the decode kernels
+// (rows % 64 == 0, k % 128 == 0):
 // one dword per lane carries the scale bytes of four 16-row MFMA fragments
 // for one 128-wide k-step, so the instruction's byte select picks the
 // fragment. out[g][s][lane][j] = scales[g*64 + j*16 + (lane & 15)]
