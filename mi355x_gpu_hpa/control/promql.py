@@ -27,14 +27,27 @@ This is used by the in-process control-loop harness (loop.py) and by the
 rule unit tests; in a real cluster the recording rule is evaluated by stock
 Prometheus (SURVEY.md C12 "reuse as-is") — parity between the two is what
 the kind-cluster integration harness checks.
+
+``evaluate`` first asks the native evaluator (native/control/promql_ext.cpp,
+``_mi355x_promql`` in the native build directory), which keeps one compiled
+plan per expression string and answers the cases it can answer exactly like
+``_eval``; for everything else, every error included, it defers and the
+Python parser and evaluator below run unchanged. They are its
+specification. ``MI355X_PROMQL_NATIVE=0`` (or ``use_native(False)``) keeps
+every call in Python.
 """
 
 from __future__ import annotations
 
+import importlib.machinery
+import importlib.util
 import math
+import os
 import re
 from dataclasses import dataclass, field
 from typing import Callable, Dict, List, Optional, Tuple
+
+from .. import NATIVE_BUILD
 
 Labels = Tuple[Tuple[str, str], ...]  # sorted, excludes __name__
 
@@ -381,8 +394,88 @@ def _eval(node: Expr, samples: Vector):
     raise PromQLError(f"unknown node {node!r}")
 
 
+# --- native evaluator (native/control/promql_ext.cpp) ----------------------
+
+# Set to 0/false/off/no to keep every evaluate() in Python (A/B runs).
+NATIVE_ENV = "MI355X_PROMQL_NATIVE"
+NATIVE_EXT_NAME = "_mi355x_promql"
+
+_ext = None             # the extension module once loaded
+_native_eval = None     # its evaluate() while the native path is on
+_native_defer = None    # its DEFER object
+_native_decided = False
+
+
+def _ext_path():
+    return NATIVE_BUILD / (NATIVE_EXT_NAME
+                           + importlib.machinery.EXTENSION_SUFFIXES[0])
+
+
+def _load_ext():
+    """The extension module, loaded from the native build directory by
+    path, or None when it is not built."""
+    global _ext
+    if _ext is None:
+        path = _ext_path()
+        if not path.is_file():
+            return None
+        spec = importlib.util.spec_from_file_location(
+            NATIVE_EXT_NAME, str(path))
+        try:
+            mod = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(mod)
+        except ImportError:
+            return None
+        mod.bind(Sample)
+        _ext = mod
+    return _ext
+
+
+def native_available() -> bool:
+    return _load_ext() is not None
+
+
+def _native_enabled_by_env() -> bool:
+    return os.environ.get(NATIVE_ENV, "1").strip().lower() not in (
+        "0", "false", "off", "no")
+
+
+def use_native(flag: Optional[bool] = None) -> bool:
+    """Switch the native path on or off (``None``: as the environment
+    says). Returns whether it is on now; it stays off when the extension
+    is not built."""
+    global _native_eval, _native_defer, _native_decided
+    if flag is None:
+        flag = _native_enabled_by_env()
+    ext = _load_ext() if flag else None
+    _native_eval = ext.evaluate if ext is not None else None
+    _native_defer = ext.DEFER if ext is not None else None
+    _native_decided = True
+    return _native_eval is not None
+
+
+def native_active() -> bool:
+    """Whether evaluate() asks the native evaluator first."""
+    if not _native_decided:
+        use_native(None)
+    return _native_eval is not None
+
+
+def native_counters() -> Optional[Dict[str, int]]:
+    """The extension's counters (handled, deferred_parse, deferred_eval,
+    compiles, cache_size), or None when it is not built."""
+    ext = _load_ext()
+    return ext.counters() if ext is not None else None
+
+
 def evaluate(expr: str, samples: Vector) -> Vector:
     """Evaluate an instant query; returns a vector (scalars are wrapped)."""
+    if not _native_decided:
+        use_native(None)
+    if _native_eval is not None:
+        res = _native_eval(expr, samples)
+        if res is not _native_defer:
+            return res
     res = _eval(parse(expr), samples)
     if isinstance(res, float):
         return [Sample("", {}, res)]
