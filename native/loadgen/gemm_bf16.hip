@@ -35,10 +35,7 @@
 // The kernel computes C[M][N] f32 = A[M][K] bf16 @ B^T[N][K] bf16.
 // M, N, K must be multiples of the tile sizes (load generator: we pick them).
 
-#include <hip/hip_runtime.h>
-
-typedef __attribute__((ext_vector_type(8))) unsigned short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "gemm_tile.h"
 
 #define BM 128
 #define BN 128
@@ -51,12 +48,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define GLDS_PER_TILE_PER_WAVE 4
 
 // st_16x32 swizzle on a byte offset within the operand tile image
-// (subtile = 1024 B = 8 rows x 128 B).
+// (subtile = 1024 B = 8 rows x 128 B); SWZ = 0 is the linear-LDS ablation.
 template <int SWZ>
 __device__ __forceinline__ int swz(int byte_off)
 {
-    if (SWZ) byte_off ^= ((byte_off >> 9) & 1) << 5;
-    return byte_off;
+    return SWZ ? swz_st16x32(byte_off) : byte_off;
 }
 
 template <int SWZ>
@@ -83,12 +79,7 @@ __device__ __forceinline__ void gemm_bf16_tn_impl(
     // XCD-aware bijective remap: consecutive tiles land on one XCD so an
     // XCD's L2 sees contiguous A-rows. q/r form handles n_tiles % 8 != 0.
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
     // Per-lane glds source for this lane's 16 B of each 1-KiB piece.
     // Piece p (wave wid, iter it: p = wid*4+it) covers LDS bytes
@@ -113,10 +104,7 @@ __device__ __forceinline__ void gemm_bf16_tn_impl(
         const long row0 = (long)tm * BM;
         const long col0 = (long)tn * BN;
 
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         const int kTiles = K / BK;
         const int piece_row0 = wid * (GLDS_PER_TILE_PER_WAVE * 8);
@@ -129,14 +117,8 @@ __device__ __forceinline__ void gemm_bf16_tn_impl(
             unsigned short* lb = &lds[TILE_HW];
 #pragma unroll
             for (int it = 0; it < GLDS_PER_TILE_PER_WAVE; ++it) {
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)(ga + (long)it * 8 * K),
-                    (__attribute__((address_space(3))) unsigned int*)(la + wid * 4 * 512 + it * 512),
-                    16, 0, 0);
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)(gb + (long)it * 8 * K),
-                    (__attribute__((address_space(3))) unsigned int*)(lb + wid * 4 * 512 + it * 512),
-                    16, 0, 0);
+                glds16(ga + (long)it * 8 * K, la + wid * 4 * 512 + it * 512);
+                glds16(gb + (long)it * 8 * K, lb + wid * 4 * 512 + it * 512);
             }
         }
 
@@ -159,14 +141,8 @@ __device__ __forceinline__ void gemm_bf16_tn_impl(
                 unsigned short* nb = &lds[(buf ^ 1) * 2 * TILE_HW + TILE_HW];
 #pragma unroll
                 for (int it = 0; it < GLDS_PER_TILE_PER_WAVE; ++it) {
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) unsigned int*)(ga + (long)it * 8 * K),
-                        (__attribute__((address_space(3))) unsigned int*)(na + wid * 4 * 512 + it * 512),
-                        16, 0, 0);
-                    __builtin_amdgcn_global_load_lds(
-                        (const __attribute__((address_space(1))) unsigned int*)(gb + (long)it * 8 * K),
-                        (__attribute__((address_space(3))) unsigned int*)(nb + wid * 4 * 512 + it * 512),
-                        16, 0, 0);
+                    glds16(ga + (long)it * 8 * K, na + wid * 4 * 512 + it * 512);
+                    glds16(gb + (long)it * 8 * K, nb + wid * 4 * 512 + it * 512);
                 }
                 asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             } else {
@@ -205,7 +181,9 @@ __device__ __forceinline__ void gemm_bf16_tn_impl(
             __builtin_amdgcn_s_barrier();
         }
 
-        // Epilogue: f32 store, coalesced by 16-lane row groups.
+        // Epilogue: f32 store, coalesced by 16-lane row groups (written
+        // out: store_acc() here changes the generated code,
+        // profiles/loadgen_refactor.md).
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll

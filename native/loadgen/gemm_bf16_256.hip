@@ -44,18 +44,9 @@
 //
 // C[M][N] f32 = A[M][K] bf16 @ B^T[N][K] bf16; M,N % 256 == 0, K % 64 == 0.
 
-#include <hip/hip_runtime.h>
-
-typedef __attribute__((ext_vector_type(8))) unsigned short bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
+#include "gemm_tile.h"
 
 #define HALF_HW 8192          // halfwords per half-tile image (128x64)
-#define HALF_BYTES 16384
-
-static __device__ __forceinline__ int swz256(int byte_off)
-{
-    return byte_off ^ (((byte_off >> 9) & 1) << 5);
-}
 
 // DEPTH selects the measured schedule variants (see the header comment and
 // profiles/gemm_bf16_256_ladder.md): 1 = depth-1 full drain; 2 = one B0
@@ -82,16 +73,11 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
     // glds source mapping for this lane's 16 B of each 1-KiB piece
     // (piece p = w*2+it covers half-image rows p*8..p*8+7).
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
@@ -99,7 +85,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl(
     // A-frag mf (0..7), k-step ks: row_in_half = mf*16 + (lane&15)
     // B-frag nf (0..3): col_in_half = (wc&1)*64 + nf*16 + (lane&15)
     auto frag_off = [&](int row_in_half, int ks) {
-        return swz256(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
+        return swz_st16x32(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
     };
 
     const int n_tiles_m = M / 256;
@@ -112,23 +98,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         // stage half `h` (0=A0,1=A1,2=B0,3=B1) of K-tile `kt` into buffer
         // `buf`; 2 glds per wave.
@@ -142,12 +117,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -316,18 +286,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl(
 
         // epilogue: per-wave 128x64 f32 store
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long row = row0 + wr * 128 + i * 16 + (lane >> 4) * 4 + r;
-                    const long col = col0 + wc * 64 + j * 16 + (lane & 15);
-                    C[row * (long)N + col] = acc[i][j][r];
-                }
-            }
-        }
+        store_acc(C, N, row0, col0, wr, wc, lane, acc);
         __syncthreads();
     }
 }
@@ -408,19 +367,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl7(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     auto frag_off = [&](int row_in_half, int ks) {
-        return swz256(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
+        return swz_st16x32(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
     };
 
     const int n_tiles_m = M / 256;
@@ -430,23 +384,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl7(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         auto stage = [&](int kt, int h, int buf) {
             if (kt >= kTiles) kt = kTiles - 1;
@@ -458,12 +401,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl7(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -539,18 +477,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl7(
         }
 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long row = row0 + wr * 128 + i * 16 + (lane >> 4) * 4 + r;
-                    const long col = col0 + wc * 64 + j * 16 + (lane & 15);
-                    C[row * (long)N + col] = acc[i][j][r];
-                }
-            }
-        }
+        store_acc(C, N, row0, col0, wr, wc, lane, acc);
         __syncthreads();
     }
 }
@@ -583,8 +510,6 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_256_d8(
 // Staging, liveness proofs, drains, swizzle and raster are d6's verbatim
 // (B is still read only at q0; A-halves live through q3).
 // ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
 extern "C" __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_256_w32(
     const unsigned short* __restrict__ A, const unsigned short* __restrict__ Bt,
     float* __restrict__ C, int M, int N, int K, int tiles_per_cta)
@@ -603,21 +528,16 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_256_w32(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     // 32x32 fragment read: row_in_half = frag_row + (lane&31),
     // k = ks16*16 + (lane>>5)*8  -> byte off swizzled
     auto frag_off32 = [&](int row_in_half, int ks16) {
-        return swz256(row_in_half * 128 + ks16 * 32 + ((lane >> 5) * 16));
+        return swz_st16x32(row_in_half * 128 + ks16 * 32 + ((lane >> 5) * 16));
     };
 
     const bool super4 = (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
@@ -626,15 +546,7 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_256_w32(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
@@ -656,12 +568,7 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_bf16_tn_256_w32(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -812,19 +719,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl9(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     auto frag_off = [&](int row_in_half, int ks) {
-        return swz256(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
+        return swz_st16x32(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
     };
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
@@ -833,23 +735,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl9(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         auto stage = [&](int kt, int h, int buf) {
             if (kt >= kTiles) kt = kTiles - 1;
@@ -861,12 +752,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl9(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -965,19 +851,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl9(
                 }
             }
         } else {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const long row =
-                            row0 + wr * 128 + i * 16 + (lane >> 4) * 4 + r;
-                        const long col = col0 + wc * 64 + j * 16 + (lane & 15);
-                        C[row * (long)N + col] = acc[i][j][r];
-                    }
-                }
-            }
+            store_acc(C, N, row0, col0, wr, wc, lane, acc);
         }
         __syncthreads();
     }
@@ -1034,19 +908,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl18(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     auto frag_off = [&](int row_in_half, int ks) {
-        return swz256(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
+        return swz_st16x32(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
     };
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
@@ -1055,23 +924,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl18(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         // A slots: lds[(abuf*2 + h) * HALF_HW], h 0/1
         // B slots: lds[(4 + bbuf*2 + hb) * HALF_HW], hb 0/1
@@ -1083,12 +941,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl18(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
         auto stage_b = [&](int kt, int hb, int bbuf) {
@@ -1099,12 +952,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl18(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -1181,18 +1029,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl18(
         }
 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long row = row0 + wr * 128 + i * 16 + (lane >> 4) * 4 + r;
-                    const long col = col0 + wc * 64 + j * 16 + (lane & 15);
-                    C[row * (long)N + col] = acc[i][j][r];
-                }
-            }
-        }
+        store_acc(C, N, row0, col0, wr, wc, lane, acc);
         __syncthreads();
     }
 }
@@ -1243,21 +1080,16 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl19(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     // linearized read addressing: swz(frag_row*128 + ks*64 + lg*16) =
     // frag*2048 + swz_base[ks] for frag_row = frag*16 + (lane&15)
-    const int swz_base0 = swz256((lane & 15) * 128 + ((lane >> 4) * 16));
-    const int swz_base1 = swz256((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
+    const int swz_base0 = swz_st16x32((lane & 15) * 128 + ((lane >> 4) * 16));
+    const int swz_base1 = swz_st16x32((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
 
@@ -1265,23 +1097,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl19(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         auto stage_a = [&](int kt, int h, int abuf) {
             if (kt >= kTiles) kt = kTiles - 1;
@@ -1291,12 +1112,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl19(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
         auto stage_b = [&](int kt, int hb, int bbuf) {
@@ -1307,12 +1123,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl19(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -1398,6 +1209,8 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl19(
         }
 
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // written out: store_acc() here changes the generated code
+        // (profiles/loadgen_refactor.md)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -1460,19 +1273,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl20(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
-    const int swz_base0 = swz256((lane & 15) * 128 + ((lane >> 4) * 16));
-    const int swz_base1 = swz256((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
+    const int swz_base0 = swz_st16x32((lane & 15) * 128 + ((lane >> 4) * 16));
+    const int swz_base1 = swz_st16x32((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
 
@@ -1480,23 +1288,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl20(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][8];  // 256 registers -> AGPR file
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         // 4 glds per wave per half (pieces w*4 .. w*4+3)
         auto stage = [&](int kt, int h, int buf) {
@@ -1509,12 +1306,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl20(
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int p = w * 4 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -1574,6 +1366,8 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl20(
             __builtin_amdgcn_s_barrier();
         }
 
+        // written out: store_acc() here changes the generated code
+        // (profiles/loadgen_refactor.md)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -1628,19 +1422,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl21(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
-    const int swz_base0 = swz256((lane & 15) * 128 + ((lane >> 4) * 16));
-    const int swz_base1 = swz256((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
+    const int swz_base0 = swz_st16x32((lane & 15) * 128 + ((lane >> 4) * 16));
+    const int swz_base1 = swz_st16x32((lane & 15) * 128 + 64 + ((lane >> 4) * 16));
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
 
@@ -1648,23 +1437,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl21(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][8];  // 256 registers -> AGPR file
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         auto stage_a = [&](int kt, int h, int abuf) {
             if (kt >= kTiles) kt = kTiles - 1;
@@ -1674,12 +1452,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl21(
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int p = w * 4 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
         auto stage_b = [&](int kt, int hb, int bbuf) {
@@ -1690,12 +1463,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl21(
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int p = w * 4 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 512),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 512);
             }
         };
 
@@ -1772,6 +1540,8 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl21(
             bbuf = bbuf1;
         }
 
+        // written out: store_acc() here changes the generated code
+        // (profiles/loadgen_refactor.md)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
 #pragma unroll
@@ -1848,19 +1618,14 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl14(
     const int kTiles = K / 64;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
-    const int in_piece = swz256(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kk = (in_piece & 127) >> 1;
 
     auto frag_off = [&](int row_in_half, int ks) {
-        return swz256(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
+        return swz_st16x32(row_in_half * 128 + ks * 64 + ((lane >> 4) * 16));
     };
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
@@ -1869,23 +1634,12 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl14(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         // one 1-KiB glds piece per wave (16 waves x 1 KiB = one half-tile)
         auto stage = [&](int kt, int h, int buf) {
@@ -1895,11 +1649,7 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl14(
                 (h < 2) ? A + (row0 + h * 128) * (long)K + k0
                         : Bt + (col0 + (h - 2) * 128) * (long)K + k0;
             unsigned short* dst = &lds[(buf * 4 + h) * HALF_HW];
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) unsigned int*)
-                    (src + (long)(w * 8 + src_row) * K),
-                (__attribute__((address_space(3))) unsigned int*)(dst + w * 512),
-                16, 0, 0);
+            glds16(src + (long)(w * 8 + src_row) * K, dst + w * 512);
         };
 
         stage(0, 0, 0);
@@ -1959,6 +1709,8 @@ __device__ __forceinline__ void gemm_bf16_tn_256_impl14(
             __builtin_amdgcn_s_barrier();
         }
 
+        // written out: store_acc() here changes the generated code
+        // (profiles/loadgen_refactor.md)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
 #pragma unroll

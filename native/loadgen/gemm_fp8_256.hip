@@ -22,18 +22,9 @@
 //
 // C[M][N] f32 = A[M][K] fp8 @ B^T[N][K] fp8; M,N % 256 == 0, K % 128 == 0.
 
-#include <hip/hip_runtime.h>
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
+#include "gemm_tile.h"
 
 #define F8_HALF_BYTES 16384   // [128][128] fp8 image
-
-static __device__ __forceinline__ int swz256b(int byte_off)
-{
-    return byte_off ^ (((byte_off >> 9) & 1) << 5);
-}
 
 // DEEPB=1: 3-deep B rotation in 160 KiB LDS (the bf16 d18 structure —
 // B staged two tiles ahead into a slot dead since the previous boundary
@@ -59,23 +50,18 @@ __device__ __forceinline__ void gemm_fp8_tn_256_impl(
     const int kTiles = K / 128;
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
     // glds source mapping (piece p = w*2+it covers image rows p*8..p*8+7;
     // 128-B rows, byte-granular k)
-    const int in_piece = swz256b(lane * 16) & 1023;
+    const int in_piece = swz_st16x32(lane * 16) & 1023;
     const int src_row = in_piece >> 7;
     const int src_kb = in_piece & 127;   // byte (= k index) within the row
 
     // fragment read byte offset: row `row_in_half`, 32-B k-chunk per lane
     // group (lane>>4), `half16` selects the chunk's low/high 16 B
     auto frag_off = [&](int row_in_half, int half16) {
-        return swz256b(row_in_half * 128 + (lane >> 4) * 32 + half16 * 16);
+        return swz_st16x32(row_in_half * 128 + (lane >> 4) * 32 + half16 * 16);
     };
 
     const bool super4 = RASTER && (n_tiles_n % 4 == 0) && (n_tiles_m % 4 == 0);
@@ -84,23 +70,12 @@ __device__ __forceinline__ void gemm_fp8_tn_256_impl(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
         f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        zero_acc(acc);
 
         // slot layout: DEEPB=0: [buf][A0 A1 B0 B1] x2 (d9 layout);
         // DEEPB=1: A [abuf][h] in slots 0-3, B [bbuf][hb] in slots 4-9
@@ -118,12 +93,7 @@ __device__ __forceinline__ void gemm_fp8_tn_256_impl(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + (long)(p * 8 + src_row) * K),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 1024),
-                    16, 0, 0);
+                glds16(src + (long)(p * 8 + src_row) * K, dst + p * 1024);
             }
         };
 
@@ -208,18 +178,7 @@ __device__ __forceinline__ void gemm_fp8_tn_256_impl(
             if (DEEPB) bbuf = bbuf + 1 >= 3 ? 0 : bbuf + 1;
         }
 
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const long row = row0 + wr * 128 + i * 16 + (lane >> 4) * 4 + r;
-                    const long col = col0 + wc * 64 + j * 16 + (lane & 15);
-                    C[row * (long)N + col] = acc[i][j][r];
-                }
-            }
-        }
+        store_acc(C, N, row0, col0, wr, wc, lane, acc);
         __syncthreads();
     }
 }

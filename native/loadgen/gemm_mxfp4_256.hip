@@ -32,40 +32,9 @@
 // C[M][N] f32 = dq(A)[M][K] @ dq(Bt)[N][K]^T; M,N % 256 == 0, K % 256 == 0.
 // A, Bt: [rows][K/2] bytes, element 2i in the low nibble.
 
-#include <hip/hip_runtime.h>
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
+#include "gemm_tile.h"
 
 #define F4_HALF_BYTES 16384   // [128][256] fp4 image, 128-B rows
-
-static __device__ __forceinline__ int swz_f4(int byte_off)
-{
-    return byte_off ^ (((byte_off >> 8) & 7) << 4);
-}
-
-// The scale byte selects must be literal constants for the builtin; after
-// unrolling, oa/ob are constants and the switch folds away.
-#define F4_MFMA(OA, OB)                                                       \
-    case (OA) * 4 + (OB):                                                     \
-        return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(              \
-            a, b, c, 4, 4, OA, sa, OB, sb)
-static __device__ __forceinline__ f32x4 mfma_mxfp4(i32x8 a, i32x8 b, f32x4 c,
-                                                   int oa, int sa, int ob,
-                                                   int sb)
-{
-    switch (oa * 4 + ob) {
-        F4_MFMA(0, 0); F4_MFMA(0, 1); F4_MFMA(0, 2); F4_MFMA(0, 3);
-        F4_MFMA(1, 0); F4_MFMA(1, 1); F4_MFMA(1, 2); F4_MFMA(1, 3);
-        F4_MFMA(2, 0); F4_MFMA(2, 1); F4_MFMA(2, 2); F4_MFMA(2, 3);
-        F4_MFMA(3, 0); F4_MFMA(3, 1); F4_MFMA(3, 2);
-        default:
-            return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                a, b, c, 4, 4, 3, sa, 3, sb);
-    }
-}
-#undef F4_MFMA
 
 extern "C" __global__ void __launch_bounds__(512, 2) gemm_mxfp4_tn_256(
     const unsigned char* __restrict__ A,   // [M][K/2] packed E2M1
@@ -91,12 +60,7 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_mxfp4_tn_256(
     const int kSteps = K / 128;  // scale dwords per lane and 64-row group
 
     const int nwg = gridDim.x;
-    int wgid = blockIdx.x;
-    {
-        int q = nwg >> 3, r = nwg & 7;
-        int xcd = wgid & 7, pos = wgid >> 3;
-        wgid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
-    }
+    const int wgid = xcd_remap(blockIdx.x, nwg);
 
     // glds source mapping: piece p = w*2+it fills image bytes
     // p*1024 + lane*16 (rows p*8..p*8+7); the lane fetches the 16 B that
@@ -119,18 +83,13 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_mxfp4_tn_256(
         const int tile = wgid + t * nwg;
         if (tile >= n_tiles) return;
         int tm, tn;
-        if (super4) {
-            const int sb = tile >> 4, wi = tile & 15;
-            const int sbn = n_tiles_n >> 2;
-            tm = (sb / sbn) * 4 + (wi >> 2);
-            tn = (sb % sbn) * 4 + (wi & 3);
-        } else {
-            tm = tile / n_tiles_n;
-            tn = tile % n_tiles_n;
-        }
+        tile_coords(tile, n_tiles_n, super4, tm, tn);
         const long row0 = (long)tm * 256;
         const long col0 = (long)tn * 256;
 
+        // zeroing and the final store are written out: zero_acc() and
+        // store_acc() here change the generated code
+        // (profiles/loadgen_refactor.md)
         f32x4 acc[8][4];
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -148,12 +107,7 @@ extern "C" __global__ void __launch_bounds__(512, 2) gemm_mxfp4_tn_256(
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
                 const int p = w * 2 + it;
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) unsigned int*)
-                        (src + src_off[it]),
-                    (__attribute__((address_space(3))) unsigned int*)
-                        (dst + p * 1024),
-                    16, 0, 0);
+                glds16(src + src_off[it], dst + p * 1024);
             }
         };
 

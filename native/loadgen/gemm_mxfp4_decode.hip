@@ -38,18 +38,8 @@
 // elements are padded to MF*16 rows with zero codes. Rows >= M are never
 // stored.
 
-#include <hip/hip_runtime.h>
+#include "gemm_tile.h"
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) int i32x4;
-typedef __attribute__((ext_vector_type(8))) int i32x8;
-
-// The scale byte selects must be literal constants for the builtin; after
-// unrolling, oa/ob are constants and the switch folds away.
-#define F4D_MFMA(OA, OB)                                                      \
-    case (OA) * 4 + (OB):                                                     \
-        return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(              \
-            a, b, c, 4, 4, OA, sa, OB, sb)
 static __device__ __forceinline__ f32x4 mfma_mxfp4_d(i32x4 a4, i32x4 b4,
                                                      f32x4 c, int oa, int sa,
                                                      int ob, int sb)
@@ -57,17 +47,8 @@ static __device__ __forceinline__ f32x4 mfma_mxfp4_d(i32x4 a4, i32x4 b4,
     // fp4 operands live in elements 0..3 only (4 VGPRs)
     const i32x8 a = {a4[0], a4[1], a4[2], a4[3], 0, 0, 0, 0};
     const i32x8 b = {b4[0], b4[1], b4[2], b4[3], 0, 0, 0, 0};
-    switch (oa * 4 + ob) {
-        F4D_MFMA(0, 0); F4D_MFMA(0, 1); F4D_MFMA(0, 2); F4D_MFMA(0, 3);
-        F4D_MFMA(1, 0); F4D_MFMA(1, 1); F4D_MFMA(1, 2); F4D_MFMA(1, 3);
-        F4D_MFMA(2, 0); F4D_MFMA(2, 1); F4D_MFMA(2, 2); F4D_MFMA(2, 3);
-        F4D_MFMA(3, 0); F4D_MFMA(3, 1); F4D_MFMA(3, 2);
-        default:
-            return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-                a, b, c, 4, 4, 3, sa, 3, sb);
-    }
+    return mfma_mxfp4(a, b, c, oa, sa, ob, sb);
 }
-#undef F4D_MFMA
 
 // Operands of two consecutive k-steps for one wave.
 template <int MF>
@@ -139,6 +120,8 @@ static __device__ __forceinline__ void decode_body(
         }
     };
 
+    // written out: zero_acc() here changes the generated code
+    // (profiles/loadgen_refactor.md)
     f32x4 acc[MF][4];
 #pragma unroll
     for (int i = 0; i < MF; ++i)

@@ -33,36 +33,7 @@
 #include <cstring>
 #include <string>
 
-extern "C" {
-const char* lg_last_error();
-int lg_device_count();
-int lg_vector_add_loop(int device, int n, int iters, double* ms_out);
-int lg_gemm_bf16_bench(int device, int m, int n, int k, int warmup, int iters,
-                       double* ms_out, double* tflops_out);
-int lg_gemm_bf16_bench_variant(int device, int m, int n, int k, int warmup,
-                               int iters, int variant, double* ms_out,
-                               double* tflops_out);
-int lg_gemm_fp8_bench(int device, int m, int n, int k, int warmup, int iters,
-                      int raster, double* ms_out, double* tflops_out);
-int lg_gemm_mxfp4_bench(int device, int m, int n, int k, int warmup, int iters,
-                        double* ms_out, double* tflops_out);
-int lg_gemm_burn(int device, double target_util_pct, double seconds,
-                 int m, int n, int k, double period_ms, volatile int* stop_flag);
-int lg_gemm_mxfp4_burn(int device, double target_util_pct, double seconds,
-                       int m, int n, int k, double period_ms,
-                       volatile int* stop_flag);
-int lg_gemm_fp8_burn(int device, double target_util_pct, double seconds,
-                     int m, int n, int k, double period_ms,
-                     volatile int* stop_flag);
-int lg_decode_mxfp4_bench(int device, int m, int n, int k, int layers,
-                          int warmup, int iters, double* ms_per_step_out,
-                          double* weight_gbps_out);
-int lg_decode_mxfp4_burn(int device, double target_util_pct, double seconds,
-                         int m, int n, int k, int layers, double period_ms,
-                         volatile int* stop_flag, double* weight_gbps_out);
-int lg_bw_burn(int device, double target_util_pct, double seconds, double gb,
-               double period_ms, volatile int* stop_flag, double* gbps_out);
-}
+#include "loadgen_api.h"
 
 static double argd(int argc, char** argv, const char* flag, double dflt)
 {

@@ -1,5 +1,5 @@
-"""The XCD-aware blockIdx remap used by both GEMM kernels
-(native/loadgen/gemm_bf16*.hip) must be a BIJECTION for every grid size —
+"""The XCD-aware blockIdx remap used by every tiled GEMM kernel (xcd_remap
+in native/loadgen/gemm_tile.h) must be a BIJECTION for every grid size —
 a non-bijective remap silently drops/duplicates output tiles (the naive
 `(b%8)*ceil(n/8)+b/8` form breaks when n%8 != 0). This replicates the
 kernel formula bit-for-bit and checks it exhaustively, plus the 4x4
