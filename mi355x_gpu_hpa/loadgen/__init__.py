@@ -1,7 +1,7 @@
 """ctypes bindings for the CDNA4 HIP load-generator library.
 
 Native side: native/loadgen/{vector_add,gemm_bf16,gemm_fp8_256,
-gemm_mxfp4_256,gemm_mxfp4_decode}.hip + loadgen_lib.cpp, built by ``make -C native loadgen``
+gemm_mxfp4_256,gemm_mxfp4_decode,attn_decode}.hip + loadgen_lib.cpp, built by ``make -C native loadgen``
 into native/build/libmi355x_loadgen.so. The MXFP4 quantizer is also built
 on its own, without HIP, into native/build/libmi355x_mxfp4.so.
 
@@ -124,6 +124,34 @@ def _load():
             ctypes.c_int, ctypes.c_double, ctypes.c_double,
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
             ctypes.c_double, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.lg_attn_decode_verify.argtypes = [
+            ctypes.c_int,
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS"),
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_double,
+        ]
+        lib.lg_attn_decode_bench.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.lg_attn_decode_bench_splits.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int,
+            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+        ]
+        lib.lg_attn_decode_burn.argtypes = [
+            ctypes.c_int, ctypes.c_double, ctypes.c_double,
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+            ctypes.c_int, ctypes.c_double, ctypes.c_void_p,
+            ctypes.POINTER(ctypes.c_double),
         ]
         lib.lg_bw_burn.argtypes = [
             ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
@@ -361,6 +389,113 @@ def decode_burn(target_util_pct: float, seconds: float, device: int = 0,
     _check(_load().lg_decode_mxfp4_burn(device, target_util_pct, seconds,
                                         batch, n, k, layers, period_ms, None,
                                         ctypes.byref(gbps)))
+    return gbps.value
+
+
+ATTN_HEAD_DIM = 128
+
+
+def _attn_args(q, k, v, seq_lens):
+    """Shape checks shared by attn_decode and attn_decode_ref; returns
+    (batch, hq, hkv, lmax, seq_lens as int32)."""
+    if q.ndim != 3 or k.ndim != 4 or v.ndim != 4:
+        raise LoadgenError("attn_decode expects q [B, Hq, D] and k, v "
+                           "[B, Hkv, Lmax, D]")
+    if k.shape != v.shape:
+        raise LoadgenError(f"attn_decode: k {k.shape} and v {v.shape} differ")
+    if q.shape[-1] != ATTN_HEAD_DIM or k.shape[-1] != ATTN_HEAD_DIM:
+        raise LoadgenError("attn_decode: head dimension must be 128")
+    batch, hq, _ = q.shape
+    hkv, lmax = k.shape[1], k.shape[2]
+    if k.shape[0] != batch:
+        raise LoadgenError("attn_decode: q and k batch dimensions differ")
+    if batch < 1 or hkv < 1 or lmax < 1:
+        raise LoadgenError("attn_decode: empty batch, heads or context")
+    if hq % hkv or hq // hkv > 16:
+        raise LoadgenError(f"attn_decode: {hq} q heads over {hkv} kv heads; "
+                           "need a multiple, at most 16 per kv head")
+    lens = np.asarray(seq_lens)
+    if lens.shape != (batch,) or lens.dtype.kind not in "iu":
+        raise LoadgenError(f"attn_decode: seq_lens must be {batch} integers")
+    if lens.min() < 1 or lens.max() > lmax:
+        raise LoadgenError(f"attn_decode: seq_lens outside 1..{lmax}")
+    return batch, hq, hkv, lmax, np.ascontiguousarray(lens, np.int32)
+
+
+def attn_decode(q: np.ndarray, k: np.ndarray, v: np.ndarray, seq_lens,
+                device: int = 0, kv_splits: int = 0, scale=None):
+    """Single-token decode attention on the GPU: q f32 [B, Hq, 128], k and
+    v f32 [B, Hkv, Lmax, 128] (converted to bf16), seq_lens [B] in 1..Lmax;
+    query head h reads kv head h // (Hq // Hkv), Hq // Hkv <= 16. Positions
+    >= seq_lens[b] are never read into the result. Returns (o f32
+    [B, Hq, 128], lse f32 [B, Hq]) with lse the natural-log sum of
+    exp(scale * q.k_i). kv_splits: 0 = the library's heuristic, > 0 forces
+    that many splits of the context across CTAs (<= ceil(Lmax/32)).
+    scale: None = 1/sqrt(128)."""
+    q = np.ascontiguousarray(q, np.float32)
+    k = np.ascontiguousarray(k, np.float32)
+    v = np.ascontiguousarray(v, np.float32)
+    batch, hq, hkv, lmax, lens = _attn_args(q, k, v, seq_lens)
+    o = np.empty((batch, hq, ATTN_HEAD_DIM), np.float32)
+    lse = np.empty((batch, hq), np.float32)
+    _check(_load().lg_attn_decode_verify(
+        device, q, k, v, lens, o, lse, batch, hq, hkv, lmax, ATTN_HEAD_DIM,
+        kv_splits, 0.0 if scale is None else float(scale)))
+    return o, lse
+
+
+def attn_decode_ref(q: np.ndarray, k: np.ndarray, v: np.ndarray, seq_lens,
+                    scale=None):
+    """float64 numpy reference of attn_decode over the arrays as given (no
+    bf16 rounding, no GPU). Slices every slab to seq_lens[b] first, so a
+    position >= seq_lens[b] is never indexed."""
+    q = np.asarray(q, np.float64)
+    k = np.asarray(k)
+    v = np.asarray(v)
+    batch, hq, hkv, _, lens = _attn_args(q, k, v, seq_lens)
+    group = hq // hkv
+    if scale is None:
+        scale = 1.0 / np.sqrt(ATTN_HEAD_DIM)
+    o = np.empty((batch, hq, ATTN_HEAD_DIM), np.float64)
+    lse = np.empty((batch, hq), np.float64)
+    for b in range(batch):
+        for h in range(hkv):
+            kk = k[b, h, :lens[b]].astype(np.float64)
+            vv = v[b, h, :lens[b]].astype(np.float64)
+            heads = slice(h * group, (h + 1) * group)
+            s = scale * (q[b, heads] @ kk.T)
+            m = s.max(axis=1, keepdims=True)
+            p = np.exp(s - m)
+            tot = p.sum(axis=1, keepdims=True)
+            o[b, heads] = (p @ vv) / tot
+            lse[b, heads] = (m + np.log(tot))[:, 0]
+    return o, lse
+
+
+def attn_decode_bench(batch=32, hq=64, hkv=8, ctx=8192, warmup=2, iters=10,
+                      device=0, kv_splits=0):
+    """Returns (ms_per_step, kv_gbps): one step is decode attention for
+    `batch` sequences of `ctx` cached positions each; kv_gbps counts the K
+    and V bytes read per step, batch * hkv * ctx * 2 * 128 * 2. kv_splits
+    as for attn_decode."""
+    ms = ctypes.c_double()
+    gbps = ctypes.c_double()
+    _check(_load().lg_attn_decode_bench_splits(
+        device, batch, hq, hkv, ctx, ATTN_HEAD_DIM, kv_splits, warmup, iters,
+        ctypes.byref(ms), ctypes.byref(gbps)))
+    return ms.value, gbps.value
+
+
+def attn_burn(target_util_pct: float, seconds: float, device: int = 0,
+              batch: int = 32, hq: int = 64, hkv: int = 8, ctx: int = 8192,
+              period_ms: float = 100.0) -> float:
+    """Duty-cycled decode-attention load at a target GPU-busy percentage
+    (the shared closed-loop duty engine over attention steps): the KV-cache
+    side of a decode pod. Returns the KV GB/s read during the busy bursts."""
+    gbps = ctypes.c_double()
+    _check(_load().lg_attn_decode_burn(device, target_util_pct, seconds,
+                                       batch, hq, hkv, ctx, ATTN_HEAD_DIM,
+                                       period_ms, None, ctypes.byref(gbps)))
     return gbps.value
 
 

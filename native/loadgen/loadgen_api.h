@@ -85,6 +85,33 @@ int lg_decode_mxfp4_burn(int device, double target_util_pct, double seconds,
                          int m, int n, int k, int layers, double period_ms,
                          volatile int* stop_flag, double* weight_gbps_out);
 
+// Decode attention over a contiguous bf16 KV cache: q_h[batch][hq][d],
+// k_h and v_h [batch][hkv][lmax][d], seq_lens[batch] in 1..lmax ->
+// o_out[batch][hq][d], lse_out[batch][hq] (natural log). d must be 128, hq
+// a multiple of hkv with at most 16 q heads per kv head; inputs are f32,
+// converted to bf16. kv_splits: 0 = the product heuristic, > 0 forces that
+// many splits of the context across CTAs (<= ceil(lmax/32)). scale <= 0
+// means 1/sqrt(d). These entries have no dimension defaults: a dimension
+// below 1 is an error, like every other bad argument, before any device
+// call. Bench and burn: every sequence is ctx long; kv_gbps is
+// batch*hkv*ctx*2*d*2 bytes / step time (burn: / GPU-active time of the
+// bursts).
+int lg_attn_decode_verify(int device, const float* q_h, const float* k_h,
+                          const float* v_h, const int* seq_lens, float* o_out,
+                          float* lse_out, int batch, int hq, int hkv, int lmax,
+                          int d, int kv_splits, double scale);
+int lg_attn_decode_bench(int device, int batch, int hq, int hkv, int ctx, int d,
+                         int warmup, int iters, double* ms_per_step_out,
+                         double* kv_gbps_out);
+// The bench with kv_splits forced (> 0) instead of the heuristic (0).
+int lg_attn_decode_bench_splits(int device, int batch, int hq, int hkv, int ctx,
+                                int d, int kv_splits, int warmup, int iters,
+                                double* ms_per_step_out, double* kv_gbps_out);
+int lg_attn_decode_burn(int device, double target_util_pct, double seconds,
+                        int batch, int hq, int hkv, int ctx, int d,
+                        double period_ms, volatile int* stop_flag,
+                        double* kv_gbps_out);
+
 #ifdef __cplusplus
 }
 #endif

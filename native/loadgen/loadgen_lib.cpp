@@ -15,6 +15,10 @@
 //   * lg_decode_mxfp4_*(): the decode half of an inference pod — a skinny-M
 //     (1..64 rows) MXFP4 GEMM streaming a ring of weight matrices from HBM
 //     (gemm_mxfp4_decode.hip): busy% high, matrix cores idle, bandwidth-bound.
+//   * lg_attn_decode_*(): the other half of a decode pod's HBM traffic —
+//     single-token attention over a contiguous bf16 KV cache with ragged
+//     sequence lengths and grouped-query heads (attn_decode.hip); its bytes
+//     per step grow with batch and context.
 //   * lg_*_verify(): run one kernel on caller-provided host data so tests
 //     can check numerics against a plain fp32 reference.
 //
@@ -91,6 +95,12 @@ LG_DECODE_KERNEL(decode_mxfp4_m64);
 #undef LG_DECODE_KERNEL
 extern "C" __global__ void decode_mxfp4_reduce(const float4*, float4*, long,
                                                int);
+extern "C" __global__ void attn_decode_bf16(
+    const unsigned short*, const unsigned short*, const unsigned short*,
+    const int*, float*, float*, float*, float*, float*, int, int, int, int, int,
+    int, float);
+extern "C" __global__ void attn_decode_merge(const float*, const float*,
+                                             const float*, float*, float*, int);
 
 #define LG_CHECK(expr)                                                        \
     do {                                                                      \
@@ -320,6 +330,58 @@ static int gemm_burn(double target_util_pct, double seconds, double period_ms,
     return duty_burn_loop(target_util_pct, seconds, period_ms, stop_flag, [&] {
         for (int b = 0; b < 4; ++b) launch();
     });
+}
+
+// Burn body shared by the step-shaped loads (decode, attention): the
+// closed-loop duty engine over bursts of `step()` launches, plus the
+// GPU-active time of the bursts and the number of steps in them, from which
+// the caller derives its byte rate.
+template <typename StepFn>
+static int step_burn(double target_util_pct, double seconds, double period_ms,
+                     volatile int* stop_flag, StepFn&& step, double& active_ms,
+                     double& steps)
+{
+    DevEvent e0, e1;
+    LG_CHECK(e0.create());
+    LG_CHECK(e1.create());
+    // calibration step: sizes the burst so that a busy slice of the
+    // default 100 ms period holds several launches
+    LG_CHECK(hipEventRecord(e0, 0));
+    step();
+    LG_CHECK(hipEventRecord(e1, 0));
+    LG_CHECK(hipDeviceSynchronize());
+    float step_ms = 0;
+    LG_CHECK(hipEventElapsedTime(&step_ms, e0, e1));
+    int per_burst = step_ms > 0 ? (int)(2.0f / step_ms) : 4;
+    if (per_burst < 4) per_burst = 4;
+    if (per_burst > 64) per_burst = 64;
+    // rate: each burst is bracketed by events of its own, read back at the
+    // next burst (the engine has synchronised by then), so the engine
+    // itself stays as it is
+    active_ms = 0;
+    steps = 0;
+    bool pending = false;
+    if (duty_burn_loop(target_util_pct, seconds, period_ms, stop_flag, [&] {
+            float dt = 0;
+            if (pending && hipEventElapsedTime(&dt, e0, e1) == hipSuccess) {
+                active_ms += dt;
+                steps += per_burst;
+            }
+            (void)hipEventRecord(e0, 0);
+            for (int b = 0; b < per_burst; ++b) step();
+            (void)hipEventRecord(e1, 0);
+            pending = true;
+        }))
+        return -1;
+    LG_CHECK(hipDeviceSynchronize());
+    if (pending) {
+        float dt = 0;
+        LG_CHECK(hipEventElapsedTime(&dt, e0, e1));
+        active_ms += dt;
+        steps += per_burst;
+    }
+    LG_CHECK(hipGetLastError());
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1062,48 +1124,249 @@ int lg_decode_mxfp4_burn(int device, double target_util_pct, double seconds,
     DecodeBufs d;
     if (decode_alloc(d, m, n, k, layers, 0)) return -1;
     if (decode_fill_random(d)) return -1;
-    DevEvent e0, e1;
-    LG_CHECK(e0.create());
-    LG_CHECK(e1.create());
-    // calibration step: sizes the burst so that a busy slice of the
-    // default 100 ms period holds several launches
-    LG_CHECK(hipEventRecord(e0, 0));
-    decode_step(d, 0);
-    LG_CHECK(hipEventRecord(e1, 0));
-    LG_CHECK(hipDeviceSynchronize());
-    float step_ms = 0;
-    LG_CHECK(hipEventElapsedTime(&step_ms, e0, e1));
-    int per_burst = step_ms > 0 ? (int)(2.0f / step_ms) : 4;
-    if (per_burst < 4) per_burst = 4;
-    if (per_burst > 64) per_burst = 64;
-    // rate: each burst is bracketed by events of its own, read back at the
-    // next burst (the engine has synchronised by then), so the engine
-    // itself stays as it is
     double active_ms = 0, steps = 0;
-    bool pending = false;
-    if (duty_burn_loop(target_util_pct, seconds, period_ms, stop_flag, [&] {
-            float dt = 0;
-            if (pending && hipEventElapsedTime(&dt, e0, e1) == hipSuccess) {
-                active_ms += dt;
-                steps += per_burst;
-            }
-            (void)hipEventRecord(e0, 0);
-            for (int b = 0; b < per_burst; ++b) decode_step(d, 0);
-            (void)hipEventRecord(e1, 0);
-            pending = true;
-        }))
+    if (step_burn(target_util_pct, seconds, period_ms, stop_flag,
+                  [&] { decode_step(d, 0); }, active_ms, steps))
         return -1;
-    LG_CHECK(hipDeviceSynchronize());
-    if (pending) {
-        float dt = 0;
-        LG_CHECK(hipEventElapsedTime(&dt, e0, e1));
-        active_ms += dt;
-        steps += per_burst;
-    }
-    LG_CHECK(hipGetLastError());
     if (weight_gbps_out && active_ms > 0)
         *weight_gbps_out =
             steps * decode_weight_bytes(d) / (active_ms * 1e-3) / 1e9;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Decode attention over a contiguous bf16 KV cache (attn_decode.hip):
+// q [B][Hq][128] against one K and one V slab of Lmax positions per
+// (sequence, kv head), ragged seq_lens, G = Hq / Hkv query heads per kv
+// head. Memory-bound by design: each cached key and value is read once per
+// step.
+// ---------------------------------------------------------------------------
+
+struct AttnBufs {
+    DevBuf<unsigned short> q;   // [batch][hq][128]
+    DevBuf<unsigned short> k;   // [batch][hkv][lmax][128]
+    DevBuf<unsigned short> vp;  // [batch][hkv][blocks][128][32], private
+    DevBuf<int> lens;           // [batch]
+    DevBuf<float> o;            // [batch][hq][128]
+    DevBuf<float> lse;          // [batch][hq]
+    DevBuf<float> ws;           // kv_splits > 1: acc, then m, then l
+    int batch = 0, hq = 0, hkv = 0, lmax = 0, blocks = 0, kv_splits = 1;
+    int blocks_per_split = 0;
+    float scale_log2e = 0;
+    size_t rows() const { return (size_t)batch * hq; }
+    size_t k_slab() const { return (size_t)lmax * 128; }     // elements
+    size_t v_slab() const { return (size_t)blocks * 4096; }  // elements
+};
+
+// Every argument the device code turns into an address is checked here,
+// before any device call. seq_lens may be null (bench, burn: all = lmax).
+static bool attn_dims_ok(int batch, int hq, int hkv, int lmax, int d,
+                         int kv_splits, const int* seq_lens)
+{
+    const char* why = nullptr;
+    if (d != 128) why = "head dimension must be 128";
+    else if (batch < 1 || hq < 1 || hkv < 1 || lmax < 1)
+        why = "batch, heads and context must be >= 1";
+    else if (hq % hkv) why = "q heads must be a multiple of kv heads";
+    else if (hq / hkv > 16) why = "at most 16 q heads per kv head";
+    else if (kv_splits < 0 || kv_splits > (lmax + 31) / 32)
+        why = "kv_splits must be in 0..ceil(lmax/32)";
+    if (why) {
+        std::snprintf(g_last_error, sizeof(g_last_error),
+                      "attn decode: %s (batch %d, hq %d, hkv %d, lmax %d, "
+                      "d %d, kv_splits %d)",
+                      why, batch, hq, hkv, lmax, d, kv_splits);
+        return false;
+    }
+    for (int b = 0; seq_lens && b < batch; ++b)
+        if (seq_lens[b] < 1 || seq_lens[b] > lmax) {
+            std::snprintf(g_last_error, sizeof(g_last_error),
+                          "attn decode: seq_lens[%d] = %d outside 1..%d", b,
+                          seq_lens[b], lmax);
+            return false;
+        }
+    return true;
+}
+
+// Product heuristic: a CTA is one (sequence, kv head, KV split). Split the
+// context across CTAs until the grid reaches two CTAs per CU (the chip has
+// 256), as long as a split keeps at least 256 positions.
+static int attn_pick_kv_splits(int batch, int hkv, int lmax)
+{
+    const long ctas = (long)batch * hkv;
+    int s = 1;
+    while (ctas * s < 512 && lmax / (s * 2) >= 256) s *= 2;
+    return s;
+}
+
+// kv_splits: 0 = heuristic. Dimensions must have passed attn_dims_ok.
+static int attn_alloc(AttnBufs& a, int batch, int hq, int hkv, int lmax,
+                      int kv_splits, double scale)
+{
+    a.batch = batch; a.hq = hq; a.hkv = hkv; a.lmax = lmax;
+    a.blocks = (lmax + 31) / 32;
+    a.kv_splits =
+        kv_splits > 0 ? kv_splits : attn_pick_kv_splits(batch, hkv, lmax);
+    a.blocks_per_split = (a.blocks + a.kv_splits - 1) / a.kv_splits;
+    if (scale <= 0) scale = 1.0 / std::sqrt(128.0);
+    a.scale_log2e = (float)(scale * 1.4426950408889634);
+    const size_t slabs = (size_t)batch * hkv;
+    LG_CHECK(a.q.alloc(a.rows() * 128 * 2));
+    LG_CHECK(a.k.alloc(slabs * a.k_slab() * 2));
+    LG_CHECK(a.vp.alloc(slabs * a.v_slab() * 2));
+    LG_CHECK(a.lens.alloc((size_t)batch * 4));
+    LG_CHECK(a.o.alloc(a.rows() * 128 * 4));
+    LG_CHECK(a.lse.alloc(a.rows() * 4));
+    if (a.kv_splits > 1)
+        LG_CHECK(a.ws.alloc((size_t)a.kv_splits * a.rows() * 130 * 4));
+    return 0;
+}
+
+// One decode-attention step: one launch over (sequence, kv head, split),
+// plus the ordered merge when the context is split across CTAs. Verify,
+// bench and burn all run this function.
+static void attn_step(const AttnBufs& a, hipStream_t stream)
+{
+    const size_t part = (size_t)a.kv_splits * a.rows();
+    float* ws_acc = a.ws;
+    float* ws_m = a.kv_splits > 1 ? ws_acc + part * 128 : nullptr;
+    float* ws_l = a.kv_splits > 1 ? ws_m + part : nullptr;
+    hipLaunchKernelGGL(attn_decode_bf16,
+                       dim3(a.batch * a.hkv * a.kv_splits), dim3(256), 0,
+                       stream, a.q.p, a.k.p, a.vp.p, a.lens.p, a.o.p, a.lse.p,
+                       ws_acc, ws_m, ws_l, a.batch, a.hq, a.hkv, a.lmax,
+                       a.blocks_per_split, a.kv_splits, a.scale_log2e);
+    if (a.kv_splits > 1)
+        hipLaunchKernelGGL(attn_decode_merge, dim3((int)a.rows()), dim3(128),
+                           0, stream, ws_acc, ws_m, ws_l, a.o.p, a.lse.p,
+                           a.kv_splits);
+}
+
+// Public V slab [lmax][128] f32 -> the kernel's private layout
+// [blocks][128][32] bf16 (attn_decode.hip): position p of a 32-block sits
+// at 8*((p%16)/4) + 4*(p/16) + p%4. Padding past lmax is zero.
+static void attn_pack_v(const float* v, int lmax, unsigned short* out)
+{
+    const int blocks = (lmax + 31) / 32;
+    std::memset(out, 0, (size_t)blocks * 4096 * 2);
+    for (int pos = 0; pos < lmax; ++pos) {
+        const int p = pos & 31;
+        const int idx = 8 * ((p & 15) >> 2) + 4 * (p >> 4) + (p & 3);
+        unsigned short* dst = out + (size_t)(pos >> 5) * 4096 + idx;
+        for (int d = 0; d < 128; ++d)
+            dst[d * 32] = f32_to_bf16(v[(size_t)pos * 128 + d]);
+    }
+}
+
+// Bench and burn: every sequence is lmax long. One (sequence, kv head)
+// slab of K and of V (filled in the private layout directly: it is a
+// permutation of random values) is generated and replicated on the device.
+static int attn_fill_random(AttnBufs& a)
+{
+    uint32_t st = 0xa77e11d1u;
+    auto gen = [](uint32_t& s) { return f32_to_bf16(lcg_unit(s)); };
+    std::vector<unsigned short> h(a.rows() * 128);
+    lcg_fill(h, st, gen);
+    LG_CHECK(hipMemcpy(a.q, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    if (fill_pair(a.k.p, a.k_slab(), a.vp.p, a.v_slab(), st, gen)) return -1;
+    const size_t slabs = (size_t)a.batch * a.hkv;
+    for (size_t s = 1; s < slabs; ++s) {
+        LG_CHECK(hipMemcpy(a.k + s * a.k_slab(), a.k, a.k_slab() * 2,
+                           hipMemcpyDeviceToDevice));
+        LG_CHECK(hipMemcpy(a.vp + s * a.v_slab(), a.vp, a.v_slab() * 2,
+                           hipMemcpyDeviceToDevice));
+    }
+    const std::vector<int> lens(a.batch, a.lmax);
+    LG_CHECK(hipMemcpy(a.lens, lens.data(), lens.size() * 4,
+                       hipMemcpyHostToDevice));
+    return 0;
+}
+
+// K and V bytes read per step when every sequence is ctx long.
+static double attn_kv_bytes(const AttnBufs& a)
+{
+    return (double)a.batch * a.hkv * a.lmax * 2 * 128 * 2;
+}
+
+int lg_attn_decode_verify(int device, const float* q_h, const float* k_h,
+                          const float* v_h, const int* seq_lens, float* o_out,
+                          float* lse_out, int batch, int hq, int hkv, int lmax,
+                          int d, int kv_splits, double scale)
+{
+    if (!attn_dims_ok(batch, hq, hkv, lmax, d, kv_splits, seq_lens)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    AttnBufs a;
+    if (attn_alloc(a, batch, hq, hkv, lmax, kv_splits, scale)) return -1;
+    const size_t slabs = (size_t)batch * hkv;
+    std::vector<unsigned short> tmp(a.rows() * 128);
+    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = f32_to_bf16(q_h[i]);
+    LG_CHECK(hipMemcpy(a.q, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
+    tmp.resize(slabs * a.k_slab());
+    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = f32_to_bf16(k_h[i]);
+    LG_CHECK(hipMemcpy(a.k, tmp.data(), tmp.size() * 2, hipMemcpyHostToDevice));
+    tmp.resize(slabs * a.v_slab());
+    for (size_t s = 0; s < slabs; ++s)
+        attn_pack_v(v_h + s * a.k_slab(), lmax, tmp.data() + s * a.v_slab());
+    LG_CHECK(hipMemcpy(a.vp, tmp.data(), tmp.size() * 2,
+                       hipMemcpyHostToDevice));
+    LG_CHECK(hipMemcpy(a.lens, seq_lens, (size_t)batch * 4,
+                       hipMemcpyHostToDevice));
+    if (run_and_fetch([&] { attn_step(a, 0); }, o_out, a.o,
+                      a.rows() * 128 * 4))
+        return -1;
+    LG_CHECK(hipMemcpy(lse_out, a.lse, a.rows() * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int lg_attn_decode_bench_splits(int device, int batch, int hq, int hkv, int ctx,
+                                int d, int kv_splits, int warmup, int iters,
+                                double* ms_per_step_out, double* kv_gbps_out)
+{
+    if (iters < 1) iters = 1;
+    if (!attn_dims_ok(batch, hq, hkv, ctx, d, kv_splits, nullptr)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    AttnBufs a;
+    if (attn_alloc(a, batch, hq, hkv, ctx, kv_splits, 0)) return -1;
+    if (attn_fill_random(a)) return -1;
+    double ms;
+    if (timed_launches(warmup, iters, [&] { attn_step(a, 0); }, &ms))
+        return -1;
+    LG_CHECK(hipGetLastError());
+    if (ms_per_step_out) *ms_per_step_out = ms;
+    if (kv_gbps_out) *kv_gbps_out = attn_kv_bytes(a) / (ms * 1e-3) / 1e9;
+    return 0;
+}
+
+int lg_attn_decode_bench(int device, int batch, int hq, int hkv, int ctx, int d,
+                         int warmup, int iters, double* ms_per_step_out,
+                         double* kv_gbps_out)
+{
+    return lg_attn_decode_bench_splits(device, batch, hq, hkv, ctx, d, 0,
+                                       warmup, iters, ms_per_step_out,
+                                       kv_gbps_out);
+}
+
+// Attention burn: the shared closed-loop duty engine over attention steps —
+// the KV-cache side of a decode pod (busy%, bandwidth-bound, bytes per step
+// set by batch and context).
+int lg_attn_decode_burn(int device, double target_util_pct, double seconds,
+                        int batch, int hq, int hkv, int ctx, int d,
+                        double period_ms, volatile int* stop_flag,
+                        double* kv_gbps_out)
+{
+    if (kv_gbps_out) *kv_gbps_out = 0;
+    burn_args(target_util_pct, period_ms);
+    if (!attn_dims_ok(batch, hq, hkv, ctx, d, 0, nullptr)) return -1;
+    LG_CHECK(hipSetDevice(device));
+    AttnBufs a;
+    if (attn_alloc(a, batch, hq, hkv, ctx, 0, 0)) return -1;
+    if (attn_fill_random(a)) return -1;
+    double active_ms = 0, steps = 0;
+    if (step_burn(target_util_pct, seconds, period_ms, stop_flag,
+                  [&] { attn_step(a, 0); }, active_ms, steps))
+        return -1;
+    if (kv_gbps_out && active_ms > 0)
+        *kv_gbps_out = steps * attn_kv_bytes(a) / (active_ms * 1e-3) / 1e9;
     return 0;
 }
 

@@ -23,6 +23,14 @@
 //                         [--n-dim 8192] [--k 8192] [--layers 16]
 //       duty-cycled decode load (busy%% high, HBM-bandwidth-bound): the
 //       load shape of a small-batch MXFP4 serving pod
+//   mi355x-loadgen attn [--batch 32] [--q-heads 64] [--kv-heads 8]
+//                       [--ctx 8192] [--iters 10]
+//       timed decode-attention steps over a contiguous bf16 KV cache (head
+//       dimension 128); prints ms per step, KV GB/s, cache footprint
+//   mi355x-loadgen attnburn --util 80 [--seconds 60] [--batch 32]
+//                       [--q-heads 64] [--kv-heads 8] [--ctx 8192]
+//       duty-cycled decode-attention load: the KV-cache side of a decode
+//       pod, HBM bytes per step set by batch and context
 //   mi355x-loadgen bwburn --util 80 [--seconds 60] [--gb 6]
 //       duty-cycled streaming-triad HBM load
 //
@@ -46,7 +54,7 @@ int main(int argc, char** argv)
 {
     if (argc < 2) {
         std::fprintf(stderr,
-                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|fp4gemm|burn|decode|decodeburn|bwburn|devices} [flags]\n");
+                     "usage: mi355x-loadgen {vectoradd|gemm|fp8gemm|fp4gemm|burn|decode|decodeburn|attn|attnburn|bwburn|devices} [flags]\n");
         return 1;
     }
     std::string mode = argv[1];
@@ -194,6 +202,47 @@ int main(int argc, char** argv)
                         "the 256 MiB Infinity Cache in part or whole; this is "
                         "not an HBM reading\n",
                         ring_mib);
+        return 0;
+    }
+    if (mode == "attn" || mode == "attnburn") {
+        int batch = (int)argd(argc, argv, "--batch", 32);
+        int hq = (int)argd(argc, argv, "--q-heads", 64);
+        int hkv = (int)argd(argc, argv, "--kv-heads", 8);
+        int ctx = (int)argd(argc, argv, "--ctx", 8192);
+        const int d = 128;
+        double ms = 0, gbps = 0;
+        int rc;
+        if (mode == "attn") {
+            int iters = (int)argd(argc, argv, "--iters", 10);
+            int warmup = (int)argd(argc, argv, "--warmup", 2);
+            rc = lg_attn_decode_bench(device, batch, hq, hkv, ctx, d, warmup,
+                                      iters, &ms, &gbps);
+        } else {
+            double util = argd(argc, argv, "--util", 80.0);
+            double seconds = argd(argc, argv, "--seconds", 60.0);
+            double period = argd(argc, argv, "--period-ms", 100.0);
+            rc = lg_attn_decode_burn(device, util, seconds, batch, hq, hkv,
+                                     ctx, d, period, nullptr, &gbps);
+        }
+        if (rc) {
+            std::fprintf(stderr, "error: %s\n", lg_last_error());
+            return 2;
+        }
+        const double cache_mib =
+            (double)batch * hkv * ctx * 2 * d * 2 / (1 << 20);
+        if (mode == "attn")
+            std::printf("attn_decode batch=%d q_heads=%d kv_heads=%d ctx=%d "
+                        "ms_per_step=%.3f kv_gbps=%.0f cache_mib=%.0f\n",
+                        batch, hq, hkv, ctx, ms, gbps, cache_mib);
+        else
+            std::printf("attnburn batch=%d q_heads=%d kv_heads=%d ctx=%d "
+                        "kv_gbps=%.0f during bursts cache_mib=%.0f\n",
+                        batch, hq, hkv, ctx, gbps, cache_mib);
+        if (cache_mib < 512)
+            std::printf("note: a %.0f MiB cache is below 512 MiB and stays in "
+                        "the 256 MiB Infinity Cache in part or whole; this is "
+                        "not an HBM reading\n",
+                        cache_mib);
         return 0;
     }
     if (mode == "bwburn") {
